@@ -8,12 +8,22 @@ p in geomspace(1e-3, 1e-1, 9), decode B device-resident storage-experiment shots
 step are sampled on the device *before* the timed region (distinct shots per
 step; on-device Philox sampler), so the timed region is decode only.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the
+headline figure needs: it samples the inputs, runs phase 1 below (W warmup + K
+timed steps), writes the last timed step's outputs if --dump-outputs DIR is given
+(DIR/iters.npy, status.npy, fail.npy, ssf_steps.npy: float32 [point][shot], the
+same for the same arguments on every run) and prints the line with the
+contract's fields and the headline's LER counts.  Everything else described
+here (phases 2-5, the CPU baseline, the roofline, the side file) runs with
+--full.
+
 Precision: the headline line (`value`, `dtype`) runs BP in f64, ldpc v1's
-message precision (its loops use double).  The same shots are then decoded in
-f32 (the stated-tolerance variant) and reported under `variants`.
+message precision (its loops use double).  With --full the same shots are then
+decoded in f32 (the stated-tolerance variant) and reported under `variants`.
 
 Output: rank 0 prints ONE JSON line of at most LINE_MAX_BYTES (the driver's
-parser; round 5's 20 KB line was not read): the contract's fields, `roofline`,
+parser; round 5's 20 KB line was not read): the contract's fields and, with
+--full, `roofline`,
 `cpu_baseline`, the LER curve as one row of failures per p (the reference's own
 record, misc/p_sweep.py:32-33) and one number + roofline fraction per extra
 config (`configs`: C3, C4 f32 / f64, C5, the reference default).  The full
@@ -24,7 +34,7 @@ Inputs: the syndrome and readout rows are bit-packed u64 words by default
 (QD_INPUT_PACKED: 48 B per shot at n = 225 instead of 333; the sampler writes
 them, the triage reads them), --inputs bytes keeps one byte per bit.
 
-Phases:
+Phases (2-5 only with --full):
   1. headline: W warmup + K timed steps, the 9 points round-robin over --streams
      HIP streams (default 9: every point on its own stream; measured 79 vs 76 M
      f64 shots/s at 5), so kernels of independent points fill each other's tails;
@@ -811,7 +821,27 @@ class Run:
         ssp = self.ssf_steps[w:].to(torch.float64).mean(dim=(0, 2)).cpu().numpy()
         return fails, conv, itp, ssp
 
+    def dump_outputs(self, out_dir):
+        """--dump-outputs: what decode_device returned in the last timed step
+        (iters, status, fail, ssf_steps; one row per sweep point, one column
+        per shot of this rank) as float32 .npy files.  The inputs are a function
+        of the arguments alone (seeded sampler, shot indices), so two builds
+        can be compared output for output.  Above DUMP_MAX_BYTES in all, every
+        array keeps the same fixed, seeded sample of the shot columns."""
+        s = self.nsteps - 1
+        arrays = {"iters": self.iters[s], "status": self.status[s], "fail": self.fail[s],
+                  "ssf_steps": self.ssf_steps[s]}
+        keep = (DUMP_MAX_BYTES - 4096) // (4 * len(arrays) * len(self.ps))  # 4096: room for the .npy headers
+        cols = None
+        if keep < self.B:
+            cols = np.sort(np.random.default_rng(SEED).choice(self.B, size=keep, replace=False))
+        os.makedirs(out_dir, exist_ok=True)
+        for name, t in arrays.items():
+            a = t.cpu().numpy()
+            np.save(os.path.join(out_dir, name + ".npy"), (a if cols is None else a[:, cols]).astype(np.float32))
 
+
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much in all
 LINE_MAX_BYTES = 8000  # the driver's parser; round 5's 20 KB line was not read (tests/test_bench_launcher.py)
 
 
@@ -852,28 +882,29 @@ def compact_line(full: dict, detail: str) -> dict:
     line["ranks_seen"] = full["ranks_seen"]
     line["ranks"] = [{"rank": x["rank"], "device": x["device"], "timed_s": _r(x["timed_s"], 6), "shots": x["shots"]}
                      for x in full["ranks"]][:16]
-    rf = full["roofline"]
-    roof = {k: _r(rf.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms",
-                                       "launches", "algorithmic_bytes_per_launch")}
-    roof["kernel"] = rf.get("kernel")
-    roof["bytes_model"] = "LDS: 32 B/edge + 16 B/check per shot-iteration of the BP kernel's shots"
-    if "mix" in rf:  # the same bytes against the read+store time floor of the kernel's LDS instruction mix
-        roof["mix"] = {"peak": _r(rf["mix"]["peak"]), "frac": _r(rf["mix"]["frac"])}
-    if "lds_busy_pmc" in rf:
-        roof["lds_busy_pmc"] = _r(rf["lds_busy_pmc"])
-    if "ceilings" in rf:
-        roof["lds_bank_conflict_ratio_pmc"] = _r(rf["ceilings"].get("lds_bank_conflict_ratio"))
-        roof["pmc_source"] = rf["ceilings"].get("source")
-    hb = rf.get("hbm", {})
-    roof["hbm"] = {"achieved": _r(hb.get("achieved")), "frac": _r(hb.get("frac")), "peak": hb.get("peak")}
-    tr = rf.get("triage", {})
-    roof["triage"] = {"kernel": tr.get("kernel"), "avg_launch_ms": _r(tr.get("avg_launch_ms")),
-                      "achieved": _r(tr.get("achieved")),
-                      "frac": _r(tr["achieved"] / HBM_PEAK_GBS) if tr.get("achieved") else None}
-    roof["ssf_kernel"] = rf.get("ssf_kernel")
-    roof["ssf_avg_launch_ms"] = _r(rf.get("ssf_avg_launch_ms"))
-    roof["isolated_step_ms"] = _r(rf.get("isolated_step_ms"))
-    line["roofline"] = roof
+    rf = full.get("roofline")  # a --full run
+    if rf is not None:
+        roof = {k: _r(rf.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms",
+                                           "launches", "algorithmic_bytes_per_launch")}
+        roof["kernel"] = rf.get("kernel")
+        roof["bytes_model"] = "LDS: 32 B/edge + 16 B/check per shot-iteration of the BP kernel's shots"
+        if "mix" in rf:  # the same bytes against the read+store time floor of the kernel's LDS instruction mix
+            roof["mix"] = {"peak": _r(rf["mix"]["peak"]), "frac": _r(rf["mix"]["frac"])}
+        if "lds_busy_pmc" in rf:
+            roof["lds_busy_pmc"] = _r(rf["lds_busy_pmc"])
+        if "ceilings" in rf:
+            roof["lds_bank_conflict_ratio_pmc"] = _r(rf["ceilings"].get("lds_bank_conflict_ratio"))
+            roof["pmc_source"] = rf["ceilings"].get("source")
+        hb = rf.get("hbm", {})
+        roof["hbm"] = {"achieved": _r(hb.get("achieved")), "frac": _r(hb.get("frac")), "peak": hb.get("peak")}
+        tr = rf.get("triage", {})
+        roof["triage"] = {"kernel": tr.get("kernel"), "avg_launch_ms": _r(tr.get("avg_launch_ms")),
+                          "achieved": _r(tr.get("achieved")),
+                          "frac": _r(tr["achieved"] / HBM_PEAK_GBS) if tr.get("achieved") else None}
+        roof["ssf_kernel"] = rf.get("ssf_kernel")
+        roof["ssf_avg_launch_ms"] = _r(rf.get("ssf_avg_launch_ms"))
+        roof["isolated_step_ms"] = _r(rf.get("isolated_step_ms"))
+        line["roofline"] = roof
     if "cpu_baseline" in full:
         cb = full["cpu_baseline"]
         line["cpu_baseline"] = {"value": _r(cb["value"]), "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -927,7 +958,8 @@ def compact_line(full: dict, detail: str) -> dict:
                                                 "fail_flags_identical": c["fail_flags_identical"]}
     if cfgs:
         line["configs"] = cfgs
-    line["detail"] = detail
+    if detail is not None:
+        line["detail"] = detail
     return line
 
 
@@ -984,7 +1016,17 @@ def main():
                     help="1 (default): the points' BP streams at the device's high priority, the SSF streams at "
                          "the default one (the dispatcher serves pending BP workgroups first: +2.5 %% against "
                          "equal priorities, profiles/r06p/); 0: equal priorities")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline phase also run everything else the benchmark measures: the second "
+                         "precision, the isolated launches + roofline, sampling + decode, the C3 / C4 / C5 / "
+                         "reference-default lines, the CPU baseline and the LER comparison with it, and write the "
+                         "side file (--detail-out); the --no-* options above select among these")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed step of the headline phase returned (iters, status, "
+                         "fail, ssf_steps of every sweep point; this rank's shots) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.iso_steps = max(1, min(args.iso_steps, args.steps))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1056,10 +1098,13 @@ def main():
     rank_rows = gather_rows([rank, -1 if fake else dev.index, run.local_elapsed, args.steps * args.batch * len(ps)])
     shots_per_point = args.steps * args.batch * world
     total_shots = shots_per_point * P
+    if args.dump_outputs and rank == 0:  # before a later phase decodes into the same arrays
+        run.dump_outputs(args.dump_outputs)
+    full = args.full  # everything below the headline phase: only with --full
 
     # ---- phase 2: the other precision on the same shots ----
     variant = None
-    if args.variant not in ("none", args.precision):
+    if full and args.variant not in ("none", args.precision):
         vdecs = decoders(args.variant)
         occ[args.variant] = occupancy(args.variant)
         set_occupancy(vdecs, occ[args.variant])
@@ -1071,7 +1116,7 @@ def main():
 
     # ---- phase 3: isolated launches (one stream) for per-kernel durations ----
     iso = {}
-    for prec, dset in [(args.precision, decs)] + ([(variant[0], variant[4])] if variant else []):
+    for prec, dset in ([(args.precision, decs)] if full else []) + ([(variant[0], variant[4])] if variant else []):
         set_occupancy(dset, 0)  # one stream: the lone-decode default
         for d in dset:
             d.set_timing(args.iso_steps)
@@ -1092,24 +1137,24 @@ def main():
 
     # ---- phase 4: sampling + decode in the timed region ----
     sd = None
-    if not args.no_sample_phase:
+    if full and not args.no_sample_phase:
         sd_elapsed = run.timed(decs, args.steps, run.streams[:1], sampler=decs[0], warm=False)
         sd = total_shots / sd_elapsed
 
     large = c4 = refdef = c3 = None
-    if rank == 0 and world == 1 and not fake and not args.no_c3:
+    if full and rank == 0 and world == 1 and not fake and not args.no_c3:
         c3 = c3_line(dev, packed=args.inputs == "packed")
-    if rank == 0 and world == 1 and not fake and not args.no_large_code:
+    if full and rank == 0 and world == 1 and not fake and not args.no_large_code:
         large = large_code_roofline(dev)
-    if rank == 0 and world == 1 and not fake and not args.no_c4:
+    if full and rank == 0 and world == 1 and not fake and not args.no_c4:
         c4 = c4_line(dev)
-    if rank == 0 and world == 1 and not fake and not args.no_reference_default:
+    if full and rank == 0 and world == 1 and not fake and not args.no_reference_default:
         refdef = reference_default_line(dev, code, cpu=not args.no_cpu_baseline)
 
     if rank == 0:
         value = total_shots / elapsed
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(code, ps, args)
         ler = {}
         for pi, p in enumerate(ps):
@@ -1117,10 +1162,11 @@ def main():
             w_h = wilson(int(fails[pi]), shots_per_point)
             row = {"failures": int(fails[pi]), "shots": shots_per_point, "ler": float(fails[pi] / shots_per_point),
                    "wilson95": list(w_h), "bp_converged_frac": float(conv[pi] / shots_per_point),
-                   "mean_bp_iters_rank0": float(itp[pi]), "mean_ssf_steps_rank0": float(ssp[pi]),
-                   "bp_kernel_ms_isolated": float(iso[args.precision][0][:, pi].mean()),
-                   "triage_ms_isolated": float(iso[args.precision][4][:, pi].mean()),
-                   "ssf_kernel_ms_isolated": float(iso[args.precision][1][:, pi].mean())}
+                   "mean_bp_iters_rank0": float(itp[pi]), "mean_ssf_steps_rank0": float(ssp[pi])}
+            if full:
+                row.update({"bp_kernel_ms_isolated": float(iso[args.precision][0][:, pi].mean()),
+                            "triage_ms_isolated": float(iso[args.precision][4][:, pi].mean()),
+                            "ssf_kernel_ms_isolated": float(iso[args.precision][1][:, pi].mean())})
             cw = None
             if cpu is not None:
                 cw = wilson(cpu["failures_per_point"][key], cpu["shots_per_point"])
@@ -1137,29 +1183,31 @@ def main():
                 row[variant[0]] = vr
             ler[key] = row
 
-        bp_ms, ssf_ms, it_iso, (bp_kernel, ssf_kernel, pre_kernel), pre_ms, listed = iso[args.precision]
-        roof = lds_roofline(bp_ms, pre_ms, listed, it_iso, args, hz, bp_kernel, ssf_kernel, ssf_ms)
-        if pre_kernel:
-            roof["pre_kernel"] = pre_kernel
-            roof["triage"]["kernel"] = pre_kernel
-        pmc = None if fake else pmc_ceilings(bp_kernel)
-        if pmc is not None:
-            src, name, k = pmc
-            dv = k["derived"]
-            roof["traffic"] = dv.get("hbm_bytes_per_dispatch")
-            roof["ceilings"] = {"source": src, "kernel": name,
-                                **{key: dv.get(key) for key in ("valu_issue_frac", "lds_frac",
-                                                                "lds_bank_conflict_ratio", "hbm_frac", "clock_ghz",
-                                                                "duration_ms", "formulas")}}
-            lf = dv.get("lds_frac")
-            if lf is not None:
-                roof["lds_busy_pmc"] = lf
-        calib = os.path.join(REPO, "profiles", "r03_hbm_calibration")
-        if os.path.isdir(calib):
-            roof["hbm"]["traffic_calibration"] = {
-                "source": os.path.relpath(calib, REPO),
-                "note": "FETCH_SIZE of this kernel equals that of a staging-only build with the BP loop compiled "
-                        "out (QDEC_CALIB_NOBP): the messages add no HBM bytes"}
+        roof = None
+        if full:
+            bp_ms, ssf_ms, it_iso, (bp_kernel, ssf_kernel, pre_kernel), pre_ms, listed = iso[args.precision]
+            roof = lds_roofline(bp_ms, pre_ms, listed, it_iso, args, hz, bp_kernel, ssf_kernel, ssf_ms)
+            if pre_kernel:
+                roof["pre_kernel"] = pre_kernel
+                roof["triage"]["kernel"] = pre_kernel
+            pmc = None if fake else pmc_ceilings(bp_kernel)
+            if pmc is not None:
+                src, name, k = pmc
+                dv = k["derived"]
+                roof["traffic"] = dv.get("hbm_bytes_per_dispatch")
+                roof["ceilings"] = {"source": src, "kernel": name,
+                                    **{key: dv.get(key) for key in ("valu_issue_frac", "lds_frac",
+                                                                    "lds_bank_conflict_ratio", "hbm_frac", "clock_ghz",
+                                                                    "duration_ms", "formulas")}}
+                lf = dv.get("lds_frac")
+                if lf is not None:
+                    roof["lds_busy_pmc"] = lf
+            calib = os.path.join(REPO, "profiles", "r03_hbm_calibration")
+            if os.path.isdir(calib):
+                roof["hbm"]["traffic_calibration"] = {
+                    "source": os.path.relpath(calib, REPO),
+                    "note": "FETCH_SIZE of this kernel equals that of a staging-only build with the BP loop compiled "
+                            "out (QDEC_CALIB_NOBP): the messages add no HBM bytes"}
 
         result = {
             "metric": METRIC, "value": value, "unit": "shots/s", "n_gpus": world, "steps": args.steps,
@@ -1192,7 +1240,8 @@ def main():
         result["ranks"] = [{"rank": int(r[0]), "device": int(r[1]), "timed_s": r[2], "shots": int(r[3]),
                             "shots_per_s": r[3] / r[2] if r[2] > 0 else None} for r in rank_rows]
         result["ranks_seen"] = len(rank_rows)
-        result["roofline"] = roof
+        if roof is not None:
+            result["roofline"] = roof
         if c3 is not None:
             result["c3_line"] = c3
         if large is not None:
@@ -1208,15 +1257,17 @@ def main():
             result["ler_overlap_all"] = {
                 "headline_vs_cpu_f64": all(r["overlaps_cpu_f64"] for r in ler.values()),
                 "variant_vs_cpu_f64": all(r[variant[0]]["overlaps_cpu_f64"] for r in ler.values()) if variant else None}
-        detail = args.detail_out if os.path.isabs(args.detail_out) else os.path.join(REPO, args.detail_out)
-        try:
-            os.makedirs(os.path.dirname(detail), exist_ok=True)
-            with open(detail, "w") as fh:
-                json.dump(_finite(result), fh, indent=1, allow_nan=False)
-        except OSError as e:  # the line still goes out; it says where the detail is not
-            detail = f"unwritten ({e})"
-        if os.path.isabs(detail) and detail.startswith(REPO + os.sep):
-            detail = os.path.relpath(detail, REPO)
+        detail = None  # the side file holds the --full record
+        if full:
+            detail = args.detail_out if os.path.isabs(args.detail_out) else os.path.join(REPO, args.detail_out)
+            try:
+                os.makedirs(os.path.dirname(detail), exist_ok=True)
+                with open(detail, "w") as fh:
+                    json.dump(_finite(result), fh, indent=1, allow_nan=False)
+            except OSError as e:  # the line still goes out; it says where the detail is not
+                detail = f"unwritten ({e})"
+            if os.path.isabs(detail) and detail.startswith(REPO + os.sep):
+                detail = os.path.relpath(detail, REPO)
         print(json.dumps(_finite(compact_line(result, detail)), allow_nan=False))
     if world > 1:
         import torch.distributed as dist

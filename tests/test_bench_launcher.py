@@ -40,12 +40,68 @@ def _run_fake(tmp_path, *extra):
     env.pop("WORLD_SIZE", None)
     detail = tmp_path / "detail.json"
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--fake-device", "--batch", "512",
-                          "--steps", "2", "--detail-out", str(detail)] + list(extra),
+                          "--steps", "2", "--full", "--detail-out", str(detail)] + list(extra),
                          capture_output=True, text=True, timeout=600, env=env, cwd="/tmp")
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
     return lines[0], detail
+
+
+def test_plain_run_is_headline_only_and_dumps_last_step_outputs(tmp_path):
+    """Without --full the benchmark runs the headline phase alone: the line keeps
+    the contract's fields and the headline's LER counts and carries none of the
+    --full blocks, and no side file is written.  --dump-outputs writes the last
+    timed step's outputs as float32 [point][shot] arrays (the stand-in fails shot
+    s of point i iff s + i is odd; the last step's shots start at an even index)."""
+    import numpy as np
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    env.pop("WORLD_SIZE", None)
+    detail, dump = tmp_path / "detail.json", tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--fake-device", "--batch",
+                          "512", "--points", "3", "--steps", "3", "--warmup", "1", "--detail-out", str(detail),
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300, env=env, cwd="/tmp")
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "config"):
+        assert k in r
+    assert r["ranks_seen"] == 1 and r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0
+    assert r["ler"]["shots"] == 3 * 512 and r["ler"]["failures"] == [768, 768, 768]
+    for k in ("roofline", "cpu_baseline", "variants", "sample_and_decode", "configs", "ler_overlap_all", "detail"):
+        assert k not in r
+    assert not detail.exists()
+    assert sorted(p.name for p in dump.iterdir()) == ["fail.npy", "iters.npy", "ssf_steps.npy", "status.npy"]
+    got = {p.stem: np.load(p) for p in dump.iterdir()}
+    for a in got.values():
+        assert a.dtype == np.float32 and a.shape == (3, 512)
+    assert np.array_equal(got["fail"], (np.arange(512)[None, :] + np.arange(3)[:, None]) % 2)
+    assert (got["iters"] == 1).all() and (got["status"] == 3).all() and (got["ssf_steps"] == 0).all()
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_a_large_output(tmp_path, monkeypatch):
+    """Above DUMP_MAX_BYTES in all, every array keeps the same seeded sample of
+    the shot columns, the same on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 4 * 4 * 2 * 100)  # room for 100 of the 1000 columns
+    run = bench.Run.__new__(bench.Run)
+    run.ps, run.B, run.nsteps = [0.01, 0.02], 1000, 2
+    base = torch.arange(2 * 2 * 1000, dtype=torch.int32).reshape(2, 2, 1000)
+    run.iters, run.ssf_steps = base, base + 1
+    run.status, run.fail = (base % 7).to(torch.uint8), (base % 2).to(torch.uint8)
+    run.dump_outputs(str(tmp_path / "a"))
+    run.dump_outputs(str(tmp_path / "b"))
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("iters", "status", "fail", "ssf_steps")}
+    assert sum(os.path.getsize(tmp_path / "a" / f"{k}.npy") for k in a) <= bench.DUMP_MAX_BYTES
+    cols = (a["iters"][1] - 3000).astype(np.int64)  # the last step's row of point 1 names its own columns
+    assert a["iters"].shape == (2, 100) and (np.diff(cols) > 0).all() and 0 <= cols[0] and cols[-1] < 1000
+    assert np.array_equal(a["ssf_steps"], a["iters"] + 1) and np.array_equal(a["fail"][1], (3000 + cols) % 2)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], np.load(tmp_path / "b" / f"{k}.npy"))
 
 
 def test_bench_line_is_bounded_and_carries_roofline_and_cpu_baseline(tmp_path):

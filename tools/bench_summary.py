@@ -1,4 +1,4 @@
-"""One-line summary of a bench.py JSON line (headline, variant, per-point
+"""One-line summary of a `bench.py --full` JSON line (headline, variant, per-point
 isolated kernel times, roofline) for GPU-session logs."""
 import json
 import sys

@@ -10,7 +10,7 @@ for r in 1 2; do
              "sp_desc:--ssf-streams 1 --stream-priority 1 --point-order desc" "sp_occ8:--ssf-streams 1 --stream-priority 1 --wave-occupancy 8" \
              "sp_s5:--ssf-streams 1 --stream-priority 1 --streams 5"; do
     name=${cfg%%:*}; flags=${cfg#*:}
-    timeout -k 10 300 python -u bench.py $F $flags --detail-out $O/${name}_$r.detail.json > $O/${name}_$r.json 2> $O/${name}_$r.err
+    timeout -k 10 300 python -u bench.py --full $F $flags --detail-out $O/${name}_$r.detail.json > $O/${name}_$r.json 2> $O/${name}_$r.err
     python -c "import json,sys; d=json.load(open('$O/${name}_$r.json')); print('$name $r', round(d['value']/1e6,2), 'M/s', d['ms_per_step'], 'ms')"
   done
 done

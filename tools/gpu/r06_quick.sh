@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu ${TESTS:-tests/test_gpu_packed.py tests/test_gpu_compact.py} > $O/tests.log 2>&1 || { tail -40 $O/tests.log; exit 1; }
 tail -2 $O/tests.log
 for r in 1 2; do
-timeout -k 10 300 python -u bench.py ${BENCH_ARGS:-} --no-c4 --no-large-code --no-reference-default --no-cpu-baseline --variant none --detail-out $O/detail_$r.json > $O/bench_$r.json 2> $O/bench_$r.err
+timeout -k 10 300 python -u bench.py --full ${BENCH_ARGS:-} --no-c4 --no-large-code --no-reference-default --no-cpu-baseline --variant none --detail-out $O/detail_$r.json > $O/bench_$r.json 2> $O/bench_$r.err
 python - <<PY
 import json; d=json.load(open('$O/bench_$r.json')); r=d['roofline']
 dd=json.load(open('$O/detail_$r.json')); pp=dd['roofline']['per_point']

@@ -10,7 +10,7 @@ tail -1 $O/tests.log
 A="--no-c3 --no-c4 --no-large-code --no-reference-default --no-cpu-baseline --variant none --iso-steps 1 --no-sample-phase"
 for r in 1 2; do
   for v in 0 1; do
-    timeout -k 10 300 python -u bench.py $A --ssf-streams $v --detail-out $O/d_$v_$r.json > $O/b_${v}_$r.json 2> $O/b_${v}_$r.err
+    timeout -k 10 300 python -u bench.py --full $A --ssf-streams $v --detail-out $O/d_$v_$r.json > $O/b_${v}_$r.json 2> $O/b_${v}_$r.err
     python -c "import json; d=json.load(open('$O/b_${v}_$r.json')); print('ssf-streams=$v', d['value']/1e6, d['ms_per_step'], [d['ler']['failures'][i] for i in (0,4,8)])"
   done
 done

@@ -1,4 +1,4 @@
-"""Split a rocprofv3 kernel trace of `bench.py` by kernel and phase, and compare
+"""Split a rocprofv3 kernel trace of `bench.py --full` by kernel and phase, and compare
 the roofline kernel's isolated-phase durations with the bench's own HIP-event
 numbers.
 
