@@ -19,7 +19,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libqdec_hip.so")
-SOURCES = ["qdec_abi.cpp", "qdec_osd.cpp", "qdec_gf2.cpp", "qdec_hgp.cpp", "qdec_bp.hip", "qdec_bp_block.hip",
+SOURCES = ["qdec_abi.cpp", "qdec_tables.cpp", "qdec_osd.cpp", "qdec_gf2.cpp", "qdec_hgp.cpp", "qdec_bp.hip", "qdec_bp_block.hip",
            "qdec_sample.hip", "qdec_osd.hip"]
 # device source compiled at run time (hipRTC, per hypergraph-product code): embedded
 # into the library as a string literal (build/gen/qdec_hgp_src.inc)

@@ -400,7 +400,7 @@ def _lut_tables(lib, h):
 
 @pytest.mark.parametrize("max_steps", [0, 2])
 def test_ssf_lut_tables_follow_the_spec(code225, oracle_lib, max_steps):
-    """The table-driven SSF kernel's tables (ssf_lut_tables, qdec_abi.cpp) on the
+    """The table-driven SSF kernel's tables (ssf_lut_tables, qdec_tables.cpp) on the
     n = 225 HGP code: every generator shares ONE 4096-entry score table (same
     4 x 3 local pattern after the canonical local-check order), and the kernel's
     step rule run on the host over those exact tables reproduces the oracle's
@@ -440,7 +440,7 @@ def test_ssf_lut_tables_follow_the_spec(code225, oracle_lib, max_steps):
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_host_only_it1_tables_equal_the_oracle_iteration_1(code225, oracle_lib, precision):
-    """The triage's iteration-1 tables (it1_tables, qdec_abi.cpp), built by a
+    """The triage's iteration-1 tables (it1_tables, qdec_tables.cpp), built by a
     host-only graph: for random per-column priors (with exact ties) and random
     syndromes, looking up each column's decision under its checks' syndrome
     pattern equals the oracle's hard decision after min-sum iteration 1
@@ -481,7 +481,7 @@ def test_host_only_it1_tables_equal_the_oracle_iteration_1(code225, oracle_lib, 
 
 def test_host_only_queue_layout(code225):
     """The queue scratch layout attach_queue allocates (queue_layout,
-    qdec_abi.cpp), computed on a host-only graph for batches around the
+    qdec_tables.cpp), computed on a host-only graph for batches around the
     64-shot tile and segment sizes: regions in order and disjoint, the compact
     list's counters on a 256-B boundary (u64 atomics) and its entry region
     16-B aligned, and enough segment capacity for every

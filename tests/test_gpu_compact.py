@@ -81,7 +81,7 @@ def test_compact_every_wave_shape(gpu_available, oracle_lib, precision, mn, monk
 
 @pytest.mark.parametrize("precision", ["f32", "f64"])
 def test_triage_iteration_one_edges(gpu_available, oracle_lib, precision):
-    """The triage's iteration-1 tables (it1_tables, qdec_abi.cpp) against the
+    """The triage's iteration-1 tables (it1_tables, qdec_tables.cpp) against the
     oracle where they are most fragile: priors with exact ties between columns
     (the m1 == L_j selection), degree-1 rows (m2 = Big), columns of degree 1..4,
     single-error shots (most converge in iteration 1) next to heavier ones; a

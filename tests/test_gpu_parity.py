@@ -385,6 +385,49 @@ def test_ssf_stream_split_and_handle_chain(gpu_available, oracle_lib):
             assert np.array_equal(outs[h][k].cpu().numpy(), ref[k][sl]), (h, k)
 
 
+def test_host_decode_behind_split_decodes_on_one_handle(gpu_available, oracle_lib):
+    """One handle, f64 min-sum + SSF at p = 0.1 (most shots fail BP, so the SSF
+    queues are in use): two split decodes (BP on one stream, SSF on the handle's
+    SSF stream, one per queue), then, with the SSF stream still set and nothing
+    synchronised in between, a host-buffer decode, which runs unsplit on the
+    handle's own stream and reuses queue 0 and the first control words behind
+    both SSF kernels.  All three results equal the oracle."""
+    import torch
+    from exp_ldpc_amd.decoder import Decoder
+    dev = torch.device("cuda", 0)
+    p, B = 0.1, 512
+    keys = ("x", "corr", "iters", "status", "ssf_steps", "fail")
+    lz = np.asarray(load_code("hgp_12_3_4_s1234").logicals.z) % 2
+    rd = _errors(np.random.default_rng(6), 3 * B, 225, p)
+    syn = np.ascontiguousarray(((HZ @ rd.T).T % 2).astype(np.uint8))
+    ref = oracle_lib.decode(HZ, p, syn, method="ms", precision="f64", max_iter=50, ssf=True, gens=HX, lz=lz,
+                            readout=rd, want_llr=False, ssf_impl="fast")
+    assert (ref["status"] & 1).mean() < 0.5 and ref["ssf_steps"].sum() > 0
+    dec = Decoder(HZ, p, method="ms", precision="f64", max_iter=50, flip_sets=HX, logicals=lz)
+    syn_d, rd_d = torch.from_numpy(syn).to(dev), torch.from_numpy(rd).to(dev)
+    outs = [{"x": torch.full((B, 225), 7, dtype=torch.uint8, device=dev),
+             "corr": torch.full((B, 225), 7, dtype=torch.uint8, device=dev),
+             "iters": torch.full((B,), 7, dtype=torch.int32, device=dev),
+             "status": torch.full((B,), 7, dtype=torch.uint8, device=dev),
+             "ssf_steps": torch.full((B,), 7, dtype=torch.int32, device=dev),
+             "fail": torch.full((B,), 7, dtype=torch.uint8, device=dev)} for _ in range(2)]
+    s1, s2 = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    torch.cuda.synchronize()  # inputs are on the device before the side streams read them
+    dec.set_ssf_stream(s2)
+    for h in (0, 1):
+        sl = slice(h * B, (h + 1) * B)
+        dec.decode_device(B, syn=syn_d[sl], readout=rd_d[sl], stream=s1.cuda_stream, **outs[h])
+    got = dec.decode(syn[2 * B:], readout=rd[2 * B:], want=keys)
+    assert "ssf" in dec.last_kernels()[1]
+    torch.cuda.synchronize()
+    dec.set_ssf_stream(None)
+    for h in (0, 1):
+        for k in keys:
+            assert np.array_equal(outs[h][k].cpu().numpy(), ref[k][h * B:(h + 1) * B]), (h, k)
+    for k in keys:
+        assert np.array_equal(got[k], ref[k][2 * B:]), ("host", k)
+
+
 def test_empty_batch_and_buffer_validation(gpu_available):
     """B = 0 is a no-op on every entry point; mistyped or short device buffers
     are rejected in Python before any launch (no out-of-bounds device access)."""

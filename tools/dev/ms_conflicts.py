@@ -2,7 +2,7 @@
 
 Counts LDS-array cycles per shot-iteration by instruction type with the
 banking rules of MI355X_MICROARCH.md §LDS, for the host layout strategy of
-qdec_abi.cpp ms_layout (variables by degree, row positions annealed for the
+qdec_tables.cpp ms_layout (variables by degree, row positions annealed for the
 scatter, state slots annealed for the gather) and for variants:
   --scatter-floor F   the scatter anneal's cost floor (ms_layout: 6)
   --state-writes      include the state ds_write_b128 groups in the slot anneal
