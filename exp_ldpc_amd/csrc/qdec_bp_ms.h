@@ -445,16 +445,23 @@ struct MsCore {
                 }
             }
 
-            // ---- syndrome test (registers only) ----
-            int bad = 0;
+            // ---- syndrome test (registers only), staged: a later round of checks
+            // is tested only when the earlier rounds are all met (most failing
+            // iterations stop at the first) ----
+            bool failed = false;
 #pragma unroll
             for (int rc = 0; rc < RC; ++rc) {
-                pres[rc] = sbit[rc] != (masked_parity<RV>(smask[rc], X) != 0);
-                bad |= pres[rc];
+                if (!failed) {  // wave-uniform
+                    pres[rc] = sbit[rc] != (masked_parity<RV>(smask[rc], X) != 0);
+                    failed = __ballot(pres[rc]) != 0ull;
+                }
             }
             wave_lds_sync();  // v2c scatter complete before the next check pass
-            if (__ballot(bad) == 0ull) return true;
+            if (!failed) return true;
         }
+        // not converged: the whole residual of the last iteration (the SSF queue's)
+#pragma unroll
+        for (int rc = 0; rc < RC; ++rc) pres[rc] = sbit[rc] != (masked_parity<RV>(smask[rc], X) != 0);
         return false;
     }
 };
