@@ -156,13 +156,11 @@ void ws_drain(qd_graph* G) {
         if (G->ssf_done_live[q]) hip_check(hipEventSynchronize(G->ssf_done[q]), "hipEventSynchronize");
 }
 
-// Attach the SSF queue scratch (capacity >= B shots) and, for wave graphs, the
-// compact shot list of lean launches to the launch arguments.
-void attach_queue(qd_graph* G, DecodeArgs& a, int method, int precision) {
+// Attach the queue scratch (capacity >= B shots) when the plan asks for the SSF
+// queue or the compact shot lists; one buffer holds both (queue_layout).
+void attach_queue(qd_graph* G, const DecodePlan& plan, DecodeArgs& a) {
     const DevGraph& g = G->dg;
-    const bool cmp = g.wave && method == QD_MIN_SUM && !G->ms_var_of_slot.empty();
-    if (a.B <= 0 || (!a.ssf && !cmp && !lds_kernel_applies(G->dg, method, precision, a)))
-        return;
+    if (a.B <= 0 || (!plan.need_queue && !plan.need_lists)) return;
     if (a.B > G->q_cap) {
         ws_drain(G);  // launches still in flight may use the old queue
         if (G->qws) hip_check(hipFree(G->qws), "hipFree queue");
@@ -178,7 +176,7 @@ void attach_queue(qd_graph* G, DecodeArgs& a, int method, int precision) {
     a.q_x = base + L.x;
     a.q_r = base + L.r;
     a.q_w = reinterpret_cast<uint64_t*>(a.q_x);
-    if (g.wave) {
+    if (plan.need_lists) {
         a.cmp_count = reinterpret_cast<unsigned long long*>(base + L.cmp_count);
         a.cmp = reinterpret_cast<uint64_t*>(base + L.cmp);
         a.cmp_cap = L.cmp_cap;
@@ -220,17 +218,17 @@ void attach_queue2(qd_graph* G, DecodeArgs& a) {
     a.q_w = reinterpret_cast<uint64_t*>(a.q_x);
 }
 
-// after a launch: a two-pass decode (its triage ran) used one counter set and
-// zeroed the other, so the next one takes the other set
-void flip_counters(qd_graph* G, const DecodeArgs& a) {
-    if (a.cmp_count_next && !G->last_pre.empty()) G->cmp_par ^= 1;
+// after a launch whose triage was enqueued: it used one counter set and zeroed
+// the other, so the next two-pass decode takes the other set
+void flip_counters(qd_graph* G, const DecodeArgs& a, bool triaged) {
+    if (a.cmp_count_next && triaged) G->cmp_par ^= 1;
 }
 
-void* message_scratch(qd_graph* G, int method, int precision, const DecodeArgs& a, size_t* bytes) {
-    size_t need = block_scratch_bytes(G->dg, method, precision, G->num_cus, a);
+void* message_scratch(qd_graph* G, const DecodePlan& plan, const DecodeArgs& a, size_t* bytes) {
+    size_t need = plan.need_scratch ? block_scratch_bytes(G->dg, plan, G->num_cus, a) : 0;
     *bytes = need;
     if (need == 0) return nullptr;
-    const size_t floor = block_scratch_floor(G->dg, method, precision, G->num_cus, a);
+    const size_t floor = block_scratch_floor(G->dg, plan, G->num_cus, a);
     // capped after an allocation failure: a request at or above the size that
     // failed keeps the reduced scratch (the launch sizes its grid from the bytes
     // it gets) instead of draining and failing the same allocation every call
@@ -267,11 +265,11 @@ void* message_scratch(qd_graph* G, int method, int precision, const DecodeArgs& 
     return G->mws;
 }
 
-// byte rows for a packed decode that does not take the two-pass path (every
-// input the call passes: syn [B][m], base and readout [B][n_data])
-void attach_unpack(qd_graph* G, DecodeArgs& a) {
-    if (!a.in_packed) return;
-    const size_t need = (size_t)a.B * ((size_t)G->dg.m + 2 * (size_t)G->dg.n_data) + 256;
+// byte rows for a packed decode whose plan expands them (every input the call
+// passes: syn [B][m], base and readout [B][n_data], each region 16-B aligned)
+void attach_unpack(qd_graph* G, const DecodePlan& plan, DecodeArgs& a) {
+    if (!plan.need_unpack) return;
+    const size_t need = unpack_region(a.B, G->dg.m) + 2 * unpack_region(a.B, G->dg.n_data) + 256;
     if (need > G->ubuf_bytes) {
         ws_drain(G);  // launches in flight may still read the old buffer
         if (G->ubuf) hip_check(hipFree(G->ubuf), "hipFree unpack buffer");
@@ -301,10 +299,10 @@ void attach_timing(qd_graph* G, DecodeArgs& a) {
 // A split SSF stream waits for that event too, so the workspace chain, which
 // continues on the SSF stream, covers the copy: the next decode's triage never
 // resets the counters while the copy still reads them.
-void note_listed(qd_graph* G, const DecodeArgs& a, hipStream_t s, hipStream_t chain) {
+void note_listed(qd_graph* G, const DecodePlan& plan, const DecodeArgs& a, hipStream_t s, hipStream_t chain) {
     if (!a.ev || !G->t_listed) return;
     const size_t slot = (size_t)(a.ev - G->tev.data()) / kTimingEvents;
-    const bool cmp = !G->last_pre.empty() && a.cmp_count;
+    const bool cmp = plan.two_pass && a.cmp_count;
     G->t_cmp[slot] = cmp ? 1 : 0;
     if (cmp)
         hip_check(hipMemcpy2DAsync(G->t_listed + slot * kCmpLists * kCmpSegs, 8, a.cmp_count, 128, 8,
@@ -373,11 +371,12 @@ DecodeArgs make_args(const qd_graph* g, const qd_params* p, int64_t B, const uin
 // (qd_graph_set_ssf_stream); the host-buffer path never splits, since it
 // copies the results back on s right behind the launch.
 void enqueue_decode(qd_graph* G, const qd_params* p, DecodeArgs& a, hipStream_t s, bool allow_split) {
-    attach_queue(G, a, p->method, p->precision);
-    attach_unpack(G, a);
+    const DecodePlan plan = plan_decode(G->dg, p->method, p->precision, a);
+    attach_queue(G, plan, a);
+    attach_unpack(G, plan, a);
     attach_timing(G, a);
     size_t sb = 0;
-    void* scr = message_scratch(G, p->method, p->precision, a, &sb);
+    void* scr = message_scratch(G, plan, a, &sb);
     const bool split = allow_split && G->ssf_stream && G->ssf_stream != s && a.ssf;
     const int qb = split ? G->q_buf : 0;
     if (split) {
@@ -394,11 +393,12 @@ void enqueue_decode(qd_graph* G, const qd_params* p, DecodeArgs& a, hipStream_t 
     for (int q = 0; q < 2; ++q)
         if (G->ssf_done_live[q] && (!split || q == qb))
             hip_check(hipStreamWaitEvent(s, G->ssf_done[q], 0), "hipStreamWaitEvent");
-    const int rc = launch_decode(G->dg, p->method, p->precision, a, G->num_cus, s, scr, sb);
+    bool triaged = false;
+    const int rc = launch_decode(G->dg, plan, a, G->num_cus, s, scr, sb, &triaged);
     note_kernels(G);
-    flip_counters(G, a);  // also after a failed BP launch: its triage zeroed the other set
+    flip_counters(G, a, triaged);  // also after a failed BP launch: its triage zeroed the other set
     if (rc != 0) throw Fail(-101, std::string("decode launch failed: ") + hipGetErrorString((hipError_t)rc));
-    note_listed(G, a, s, s);
+    note_listed(G, plan, a, s, s);
     if (split) {  // the SSF kernel runs on its own stream behind this decode's BP
         if (!G->ssf_done[qb])
             hip_check(hipEventCreateWithFlags(&G->ssf_done[qb], hipEventDisableTiming), "hipEventCreate");
@@ -1004,6 +1004,40 @@ int qd_graph_queue_layout(const qd_graph* G, int64_t B, int64_t* out) {
         const QueueLayout L = queue_layout(G->dg, B);
         const int64_t v[8] = {(int64_t)L.bytes, (int64_t)L.idx, (int64_t)L.x, (int64_t)L.r, (int64_t)L.cmp_count,
                               (int64_t)L.cmp, L.cmp_cap, (int64_t)cmp_entry_bytes(G->dg)};
+        std::memcpy(out, v, sizeof(v));
+    });
+}
+
+int qd_graph_plan(const qd_graph* G, const qd_params* p, int64_t B, uint32_t present, int32_t* out) {
+    return guarded([&] {
+        check_graph(G);
+        if (!p || B <= 0 || !out) throw Fail(-8, "null params, invalid batch or null output");
+        if (p->method != QD_MIN_SUM && p->method != QD_PRODUCT_SUM) throw Fail(-3, "unknown BP method");
+        if (p->precision != QD_F32 && p->precision != QD_F64) throw Fail(-4, "unknown precision");
+        if (p->ssf && G->dg.n_gen <= 0) throw Fail(-6, "SSF requested but the graph has no flip sets");
+        // the planner reads only whether a buffer is present and how its rows
+        // are aligned: stand-in addresses, never dereferenced
+        const bool aligned = present & QD_PLAN_ROWS_ALIGNED;
+        auto in = [&](uint32_t bit) { return reinterpret_cast<uint8_t*>((present & bit) ? (aligned ? 64 : 65) : 0); };
+        auto io = [&](uint32_t bit) { return reinterpret_cast<uint8_t*>((present & bit) ? 64 : 0); };
+        DecodeArgs a{};
+        a.B = B;
+        a.max_iter = p->max_iter > 0 ? p->max_iter : G->dg.n;
+        a.ssf = p->ssf ? 1 : 0;
+        a.syn_flags = p->syn_flags & 3;
+        a.in_packed = (p->syn_flags & QD_INPUT_PACKED) ? 1 : 0;
+        a.ms_scaling = p->ms_scaling;
+        a.syn = in(QD_PLAN_SYN);
+        a.base = io(QD_PLAN_BASE);
+        a.readout = in(QD_PLAN_READOUT);
+        a.x_out = io(QD_PLAN_X);
+        a.corr_out = io(QD_PLAN_CORR);
+        a.llr_out = io(QD_PLAN_LLR);
+        a.fail = io(QD_PLAN_FAIL);
+        const DecodePlan plan = plan_decode(G->dg, p->method, p->precision, a);
+        const int32_t v[8] = {plan.bp, plan.ssf, plan.two_pass, plan.expand_packed, plan.fuse, plan.q_rpar,
+                              plan.placement,
+                              plan.need_queue | plan.need_lists << 1 | plan.need_unpack << 2 | plan.need_scratch << 3};
         std::memcpy(out, v, sizeof(v));
     });
 }

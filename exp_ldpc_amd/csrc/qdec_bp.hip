@@ -893,109 +893,106 @@ static int launch_ssf_wave(const DevGraph& g, const DecodeArgs& a, int num_cus, 
     // the fused failure check reads the dense logical table's LDS copy (as launch_bp_wave)
     if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
     const size_t lds = SsfLds<RG>::shared_bytes(g) + kSsfWaves * SsfLds<RG>::wave_bytes(g);
-    if (lds > 64 * 1024) {
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(ssf_wave_kernel<RG, XW, RW>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return (int)ea;
-    }
-    int per_cu = 0;
-    hipError_t e =
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ssf_wave_kernel<RG, XW, RW>, 64 * kSsfWaves, lds);
-    if (e != hipSuccess) return (int)e;
-    if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-    long long grid = (long long)num_cus * per_cu;
-    const long long need = (a.B + kSsfWaves - 1) / kSsfWaves;  // queue length <= B
-    if (grid > need) grid = need;
-    if (grid <= 0) return 0;
     QDEC_NOTE_SSF("qdec::ssf_wave_kernel", RG, XW, RW);
-    hipLaunchKernelGGL((ssf_wave_kernel<RG, XW, RW>), dim3((unsigned)grid), dim3(64 * kSsfWaves), lds, stream, g, a);
-    return (int)hipGetLastError();
+    return launch_resident(ssf_wave_kernel<RG, XW, RW>, 64 * kSsfWaves, lds, num_cus,
+                           (a.B + kSsfWaves - 1) / kSsfWaves /* queue length <= B */, stream, {}, g, a);
 }
 
 template <int RG, int XW, int RW, bool LEAN>
 static int launch_ssf_lut_t(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream) {
     const size_t lds = SsfLutLds::shared_bytes(g) + kLutWaves * SsfLutLds::wave_bytes(g);
     if (lds > 160 * 1024) return (int)hipErrorInvalidConfiguration;
-    if (lds > 64 * 1024) {
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(ssf_lut_kernel<RG, XW, RW, LEAN>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return (int)ea;
-    }
-    int per_cu = 0;
-    hipError_t e =
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ssf_lut_kernel<RG, XW, RW, LEAN>, 64 * kLutWaves, lds);
-    if (e != hipSuccess) return (int)e;
-    if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-    long long grid = (long long)num_cus * per_cu;
-    const long long need = (a.B + kLutWaves - 1) / kLutWaves;  // queue length <= B
-    if (grid > need) grid = need;
-    if (grid <= 0) return 0;
     QDEC_NOTE_SSF("qdec::ssf_lut_kernel", RG, XW, RW, LEAN);
-    hipLaunchKernelGGL((ssf_lut_kernel<RG, XW, RW, LEAN>), dim3((unsigned)grid), dim3(64 * kLutWaves), lds, stream, g,
-                       a);
-    return (int)hipGetLastError();
+    return launch_resident(ssf_lut_kernel<RG, XW, RW, LEAN>, 64 * kLutWaves, lds, num_cus,
+                           (a.B + kLutWaves - 1) / kLutWaves /* queue length <= B */, stream, {}, g, a);
 }
 
 template <int RG, int XW, int RW>
-static int launch_ssf_lut(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream) {
+static int launch_ssf_lut(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                          hipStream_t stream) {
     if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
-    const bool lean = !a.x_out && !a.corr_out && !a.base && g.fold_blocks == 1;
-    return lean ? launch_ssf_lut_t<RG, XW, RW, true>(g, a, num_cus, stream)
-                : launch_ssf_lut_t<RG, XW, RW, false>(g, a, num_cus, stream);
+    return p.ssf_lean ? launch_ssf_lut_t<RG, XW, RW, true>(g, a, num_cus, stream)
+                      : launch_ssf_lut_t<RG, XW, RW, false>(g, a, num_cus, stream);
 }
 
+// one-wave BP blocks, each taking shots (or list chunks) until none are left
 template <typename K>
-static int launch_persistent(K kern, size_t lds, int64_t work, int num_cus, hipStream_t stream, const DevGraph& g,
-                             const DecodeArgs& a, int block = 64, int max_per_cu = 0) {
-    if (lds > 64 * 1024) {  // e.g. a large LDS copy of the logicals (lz_in_lds)
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return (int)ea;
-    }
-    int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, block, lds);
-    if (e != hipSuccess) return (int)e;
-    if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-    if (max_per_cu > 0 && per_cu > max_per_cu) per_cu = max_per_cu;
-    // one-wave blocks: a multiple of 4 per CU puts the same number of waves on
-    // every SIMD (11 f64 waves would sit 3/3/3/2 and run slower than 8)
-    if (block == 64 && per_cu > 4) per_cu &= ~3;
-    long long grid = (long long)num_cus * per_cu;
-    if (grid > work) grid = work;
-    if (grid <= 0) return 0;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds, stream, g, a);
-    return (int)hipGetLastError();
+static int launch_persistent(K kern, size_t lds, int num_cus, hipStream_t stream, const DevGraph& g,
+                             const DecodeArgs& a, int max_per_cu = 0) {
+    return launch_resident(kern, 64, lds, num_cus, a.B, stream, GridRule{max_per_cu, true}, g, a);
 }
 
-// BP kernel of a wave shape: min-sum uses the compressed-state kernel, product-sum
-// the message-array kernel.
-// Lean launches: no x / corr / llr outputs, no base, no syndrome flags, no fold.
-static bool lean_launch(const DevGraph& g, const DecodeArgs& a, bool defer) {
-    return !a.x_out && !a.corr_out && !a.llr_out && !a.base && !a.syn_flags && g.fold_blocks == 1 &&
-           (!defer || a.q_packed);
-}
-
-// The two-pass compact path (ms_triage_kernel + bp_ms_cmp_kernel) serves lean
-// min-sum launches whose graph has the slot-order logicals (or no fused check);
-// QDEC_COMPACT=0 keeps the one-pass kernel (A/B, parity tests run both).
-static bool compact_launch(const DevGraph& g, const DecodeArgs& a, bool defer) {
-    // the triage reads 16-B chunks of byte rows (16-B aligned syndrome / readout
-    // buffers only) or u64 words of packed rows (8-B aligned, checked by the ABI);
-    // its list counters take u64 atomics (natural alignment), entries 16-B stores
+// ---------------------------------------------------------------- launch plan
+// Wave graphs.  Lean launches: no x / corr / llr outputs, no base, no syndrome
+// flags, no fold (and, with SSF, the packed queue).  The two-pass path
+// (ms_triage_kernel + bp_ms_cmp_kernel) serves lean min-sum launches whose graph
+// has the slot-order logicals (or no fused check) and whose rows the triage can
+// load: 16-B aligned byte rows, 8-B aligned packed rows.  QD_OPT_COMPACT = 0
+// keeps the one-pass kernel (A/B, parity tests run both).
+static void plan_decode_wave(const DevGraph& g, const DecodeArgs& a, DecodePlan& p) {
+    // the wave SSF kernels read the packed queue (register-owned generators, u8 local-check ids)
+    const bool ssf_wave = g.n_gen <= 128 && g.g_lc8;
+    p.placement = 3;
+    p.q_packed = a.ssf && ssf_wave ? 1 : 0;
+    const bool plain = !a.x_out && !a.corr_out && !a.llr_out && !a.base && !a.syn_flags && g.fold_blocks == 1;
+    p.lean = plain && (!a.ssf || p.q_packed);
     const uintptr_t al = a.in_packed ? 7 : 15;
-    if ((reinterpret_cast<uintptr_t>(a.syn) & al) || (a.readout && (reinterpret_cast<uintptr_t>(a.readout) & al)))
-        return false;
-    if ((reinterpret_cast<uintptr_t>(a.cmp_count) & 127) || (reinterpret_cast<uintptr_t>(a.cmp) & 15)) return false;
+    const bool aligned = !(reinterpret_cast<uintptr_t>(a.syn) & al) &&
+                         !(a.readout && (reinterpret_cast<uintptr_t>(a.readout) & al));
     const bool want_fail = a.fail && a.readout && g.k > 0;
-    return g.opt_compact && a.cmp && a.cmp_count && a.syn && lean_launch(g, a, defer) && (!want_fail || g.ms_lzs);
+    // g.ms_vslot: the slot tables the compact kernel reads are built.  With SSF
+    // the queue entries carry readout parities, whose area holds n_pad / 64
+    // words: up to n_pad logicals
+    p.two_pass = p.method == 1 && g.ms_vslot && g.opt_compact && a.syn && aligned && p.lean &&
+                 (!want_fail || g.ms_lzs) && (!a.ssf || g.k <= g.n_pad);
+    p.q_rpar = p.two_pass && a.ssf ? 1 : 0;
+    p.bp = p.method != 1 ? kBpWave : p.two_pass ? kBpTwoPass : kBpMsWave;
+    // packed rows: the triage steps through m_pad / 64 words per syndrome row,
+    // the rows hold ceil(m / 64); every other reader wants byte rows
+    p.expand_packed = a.in_packed && !(p.two_pass && g.m_pad / 64 == (g.m + 63) / 64);
+    const bool lut = g.s_lut && g.s_tog && g.opt_ssf == kSsfAuto;
+    if (!a.ssf) {
+        p.ssf = kFinNone;
+    } else if (p.q_rpar && g.opt_ssf_fuse && lut) {
+        // the compact BP kernel runs the table-driven SSF itself (QD_OPT_SSF_FUSE;
+        // same tables and spec as ssf_lut_kernel)
+        p.ssf = kFinFused;
+        p.fuse = g.n_gen <= 64 ? 1 : 2;
+    } else if (!ssf_wave) {
+        p.ssf = ssf_fin_path(g, a);
+    } else if (lut) {
+        p.ssf = kFinLut;
+        p.ssf_lean = !a.x_out && !a.corr_out && !a.base && g.fold_blocks == 1;
+    } else {
+        p.ssf = g.opt_ssf == kSsfScanGather    ? kFinScanGather
+                : g.opt_ssf == kSsfScanNoSplit ? kFinScanNoSplit
+                                               : kFinScan;
+    }
+}
+
+DecodePlan plan_decode(const DevGraph& g, int method, int precision, const DecodeArgs& a) {
+    DecodePlan p{};
+    p.method = method;
+    p.precision = precision;
+    if (g.wave && wave_kernel_supports(g)) plan_decode_wave(g, a, p);
+    else plan_decode_block(g, a, p);
+    p.defer = p.ssf != kFinNone && p.ssf != kFinFused;
+    p.need_queue = p.ssf != kFinNone;
+    p.need_lists = p.two_pass;
+    p.need_unpack = p.expand_packed;
+    return p;
 }
 
 template <int RC, int RV>
 static int launch_triage(const DevGraph& g, const DecodeArgs& a, hipStream_t stream) {
     const bool want_fail = a.fail && a.readout && g.k > 0;
-    // the tile loads are 16-B vector loads (packed rows: u64 loads)
+    // the tile loads are 16-B vector loads (packed rows: u64 loads); the list
+    // counters take u64 atomics on their own 128-B lines, entries 16-B stores
     const uintptr_t al = a.in_packed ? 7 : 15;
     if ((reinterpret_cast<uintptr_t>(a.syn) & al) || (want_fail && (reinterpret_cast<uintptr_t>(a.readout) & al)))
+        return (int)hipErrorInvalidValue;
+    if (!a.cmp || !a.cmp_count || (reinterpret_cast<uintptr_t>(a.cmp_count) & 127) ||
+        (reinterpret_cast<uintptr_t>(a.cmp) & 15))
         return (int)hipErrorInvalidValue;
     if (a.it1_lut && (!g.it1_vchk || !g.it1_cvar || g.m_pad != 64 * RC || g.n_pad != 64 * RV))
         return (int)hipErrorInvalidValue;
@@ -1023,24 +1020,26 @@ static int launch_triage(const DevGraph& g, const DecodeArgs& a, hipStream_t str
     return (int)hipGetLastError();
 }
 
+// BP kernel of a wave shape: min-sum uses the compressed-state kernels, product-sum
+// the message-array kernel.
 template <typename T, int METHOD, int RC, int RV, int DRC, bool DEFER, int FUSE = 0>
-static int launch_bp_wave(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream) {
+static int launch_bp_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                          hipStream_t stream, bool* triaged) {
     if constexpr (METHOD == 1) {
         // the fused failure check reads the dense logical table's LDS copy
         // (lz_in_lds); wave-kernel graphs always have one (n <= 576)
         if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
         const size_t lds = MsLds<T>::template bytes<RC, RV>(g);
-        const bool two_pass = a.q_rpar || (!DEFER && compact_launch(g, a, DEFER));
-        if (a.wave_ctr && !two_pass) {  // ShotSeq's chunk counter (two passes: the triage zeroes it)
+        if (a.wave_ctr && !p.two_pass) {  // ShotSeq's chunk counter (two passes: the triage zeroes it)
             const hipError_t e = hipMemsetAsync(a.wave_ctr, 0, sizeof(unsigned long long), stream);
             if (e != hipSuccess) return (int)e;
         }
-        const bool lean = lean_launch(g, a, DEFER);
+        const bool lean = p.lean;
         // f64: 2 waves per SIMD measured faster than 3 for a lone decode at every
         // p (n = 225: 7.1 vs 9.3 ms per 2^18 shots at p = 0.1); concurrent
         // decodes may ask for more (qd_graph_set_wave_occupancy)
         const int cap = g.wave_occ > 0 ? g.wave_occ : (sizeof(T) == 8 ? 8 : 0);
-        if (two_pass) {  // triage, then the listed shots
+        if (p.two_pass) {  // triage, then the listed shots
             DecodeArgs b = a;
             b.cmp_zero_ok = (g.ms_allpos >> (sizeof(T) == 4 ? 1 : 0)) & 1;
             // iteration 1 in the triage: the tables assume alpha_1 = 0.5 (the
@@ -1054,6 +1053,7 @@ static int launch_bp_wave(const DevGraph& g, const DecodeArgs& a, int num_cus, h
             }
             int rc = launch_triage<RC, RV>(g, b, stream);
             if (rc != 0) return rc;
+            *triaged = true;
             if (b.ev) (void)hipEventRecord(b.ev[3], stream);  // end of the pre-pass
             size_t clds = MsLds<T>::core_bytes(g) + ((size_t)g.k * RV * 8 + 15) / 16 * 16 +
                           2 * kCmpLists * kCmpSegs * 8;
@@ -1069,18 +1069,18 @@ static int launch_bp_wave(const DevGraph& g, const DecodeArgs& a, int num_cus, h
                     if constexpr (sizeof(T) == 8) {
                         if (cap > 8) {  // 3 waves per SIMD
                             QDEC_NOTE_BP("qdec::bp_ms_cmp_kernel", tname<T>(), RC, RV, DRC, DEFER, 2, 3, FUSE);
-                            return launch_persistent(bp_ms_cmp_kernel<T, RC, RV, DRC, DEFER, 2, 3, FUSE>, clds, b.B,
-                                                     num_cus, stream, g, b, 64, cap);
+                            return launch_persistent(bp_ms_cmp_kernel<T, RC, RV, DRC, DEFER, 2, 3, FUSE>, clds,
+                                                     num_cus, stream, g, b, cap);
                         }
                     }
                     QDEC_NOTE_BP("qdec::bp_ms_cmp_kernel", tname<T>(), RC, RV, DRC, DEFER, 2, 0, FUSE);
-                    return launch_persistent(bp_ms_cmp_kernel<T, RC, RV, DRC, DEFER, 2, 0, FUSE>, clds, b.B, num_cus,
-                                             stream, g, b, 64, cap);
+                    return launch_persistent(bp_ms_cmp_kernel<T, RC, RV, DRC, DEFER, 2, 0, FUSE>, clds, num_cus,
+                                             stream, g, b, cap);
                 }
             }
             QDEC_NOTE_BP("qdec::bp_ms_cmp_kernel", tname<T>(), RC, RV, DRC, DEFER, 0, 0, FUSE);
-            return launch_persistent(bp_ms_cmp_kernel<T, RC, RV, DRC, DEFER, 0, 0, FUSE>, clds, b.B, num_cus, stream,
-                                     g, b, 64, cap);
+            return launch_persistent(bp_ms_cmp_kernel<T, RC, RV, DRC, DEFER, 0, 0, FUSE>, clds, num_cus, stream, g, b,
+                                     cap);
         }
         // degree-3 rounds: the (2, 4, 7) shape (n = 225 HGP: 144 degree-3 columns) instantiates D3R = 2
         if constexpr (RC == 2 && RV == 4 && DRC == 7) {
@@ -1088,60 +1088,55 @@ static int launch_bp_wave(const DevGraph& g, const DecodeArgs& a, int num_cus, h
                 if constexpr (sizeof(T) == 8) {
                     if (lean && cap > 8) {  // 3 waves per SIMD: the 168-VGPR build
                         QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, true, 2, 3);
-                        return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, true, 2, 3>, lds, a.B,
-                                                 num_cus, stream, g, a, 64, cap);
+                        return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, true, 2, 3>, lds, num_cus,
+                                                 stream, g, a, cap);
                     }
                 }
                 if (lean) {
                     QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, true, 2, 0);
-                    return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, true, 2>, lds, a.B, num_cus,
-                                             stream, g, a, 64, cap);
+                    return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, true, 2>, lds, num_cus, stream,
+                                             g, a, cap);
                 }
                 QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, false, 2, 0);
-                return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, false, 2>, lds, a.B, num_cus,
-                                         stream, g, a, 64, cap);
+                return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, false, 2>, lds, num_cus, stream, g,
+                                         a, cap);
             }
         }
         if (lean) {
             QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, true, 0, 0);
-            return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, true, 0>, lds, a.B, num_cus, stream, g, a,
-                                     64, cap);
+            return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, true, 0>, lds, num_cus, stream, g, a,
+                                     cap);
         }
         QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, false, 0, 0);
-        return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, false, 0>, lds, a.B, num_cus, stream, g, a,
-                                 64, cap);
+        return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, false, 0>, lds, num_cus, stream, g, a, cap);
     } else {
         const size_t lds = (wave_lds_bytes<T>(g) + 15) / 16 * 16;
         QDEC_NOTE_BP("qdec::bp_wave_kernel", tname<T>(), METHOD, RC, RV, DRC, DEFER);
-        return launch_persistent(bp_wave_kernel<T, METHOD, RC, RV, DRC, DEFER>, lds, a.B, num_cus, stream, g, a);
+        return launch_persistent(bp_wave_kernel<T, METHOD, RC, RV, DRC, DEFER>, lds, num_cus, stream, g, a);
     }
 }
 
 template <typename T, int METHOD, int RC, int RV, int DRC>
-static int launch_wave(const DevGraph& g, const DecodeArgs& a0, int num_cus, hipStream_t stream) {
+static int launch_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a0, int num_cus, hipStream_t stream,
+                       bool* triaged) {
     DecodeArgs a = a0;
-    // the wave SSF kernel reads the packed queue (register-owned generators, u8 local-check ids)
-    const bool ssf_wave = g.n_gen <= 128 && g.g_lc8;
-    a.q_packed = a.ssf && ssf_wave ? 1 : 0;
+    a.q_packed = p.q_packed;
     a.q_w = reinterpret_cast<uint64_t*>(a.q_x);
-    // compact path with SSF: the queue entries carry readout parities
-    // (the entry's readout area holds RV words: up to 64 RV logicals)
-    a.q_rpar = (METHOD == 1 && a.ssf && ssf_wave && g.k <= 64 * RV && compact_launch(g, a, true)) ? 1 : 0;
-    if (!a.ssf) {
+    a.q_rpar = p.q_rpar;
+    if (p.ssf == kFinNone) {
         record_ev(a, 0, stream);
-        const int rc = launch_bp_wave<T, METHOD, RC, RV, DRC, false>(g, a, num_cus, stream);
+        const int rc = launch_bp_wave<T, METHOD, RC, RV, DRC, false>(g, p, a, num_cus, stream, triaged);
         record_ev(a, 1, stream);
         record_ev(a, 2, stream);
         return rc;
     }
     if (!a.q_count || !a.q_idx || !a.q_x || !a.q_r) return (int)hipErrorInvalidValue;
     if constexpr (METHOD == 1) {
-        // fused SSF: the compact BP kernel runs the table-driven SSF itself
-        // (QD_OPT_SSF_FUSE; same tables and spec as ssf_lut_kernel)
-        if (a.q_rpar && g.opt_ssf_fuse && g.s_lut && g.s_tog && g.opt_ssf == kSsfAuto && g.n_gen <= 128) {
+        if (p.ssf == kFinFused) {
             record_ev(a, 0, stream);
-            const int rc = g.n_gen <= 64 ? launch_bp_wave<T, METHOD, RC, RV, DRC, true, 1>(g, a, num_cus, stream)
-                                         : launch_bp_wave<T, METHOD, RC, RV, DRC, true, 2>(g, a, num_cus, stream);
+            const int rc = p.fuse == 1
+                               ? launch_bp_wave<T, METHOD, RC, RV, DRC, true, 1>(g, p, a, num_cus, stream, triaged)
+                               : launch_bp_wave<T, METHOD, RC, RV, DRC, true, 2>(g, p, a, num_cus, stream, triaged);
             record_ev(a, 1, stream);
             record_ev(a, 2, stream);
             return rc;
@@ -1154,39 +1149,41 @@ static int launch_wave(const DevGraph& g, const DecodeArgs& a0, int num_cus, hip
         if (e != hipSuccess) return (int)e;
     }
     record_ev(a, 0, stream);
-    int rc = launch_bp_wave<T, METHOD, RC, RV, DRC, true>(g, a, num_cus, stream);
+    int rc = launch_bp_wave<T, METHOD, RC, RV, DRC, true>(g, p, a, num_cus, stream, triaged);
     record_ev(a, 1, stream);
     if (rc != 0) return rc;
-    if (ssf_wave) {
-        hipStream_t ss = stream;
-        if (a.ssf_stream && a.ssf_stream != stream && a.ssf_ev) {  // SSF behind an event on its own stream
-            hipError_t e2 = hipEventRecord(a.ssf_ev, stream);
-            if (e2 == hipSuccess) e2 = hipStreamWaitEvent(a.ssf_stream, a.ssf_ev, 0);
-            if (e2 != hipSuccess) return (int)e2;
-            ss = a.ssf_stream;
-        }
-        if (g.s_lut && g.s_tog && g.opt_ssf == kSsfAuto) {
-            rc = g.n_gen <= 64 ? launch_ssf_lut<1, RV, RC>(g, a, num_cus, ss)
-                               : launch_ssf_lut<2, RV, RC>(g, a, num_cus, ss);
-        } else {
-            DevGraph gs = g;  // QD_SSF_SCAN_GATHER: no incremental local syndromes
-            if (g.opt_ssf == kSsfScanGather) gs.g_inv = nullptr;
-            rc = g.n_gen <= 64 ? launch_ssf_wave<1, RV, RC>(gs, a, num_cus, ss)
-                               : launch_ssf_wave<2, RV, RC>(gs, a, num_cus, ss);
-        }
-        record_ev(a, 2, ss);
+    if (p.ssf == kFinIncBlock || p.ssf == kFinBlockLds) {  // generators the wave SSF kernels do not hold
+        rc = launch_ssf_block(g, p, a, num_cus, stream);
+        record_ev(a, 2, stream);
         return rc;
     }
-    rc = launch_ssf_block(g, a, num_cus, stream);
-    record_ev(a, 2, stream);
+    hipStream_t ss = stream;
+    if (a.ssf_stream && a.ssf_stream != stream && a.ssf_ev) {  // SSF behind an event on its own stream
+        hipError_t e2 = hipEventRecord(a.ssf_ev, stream);
+        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(a.ssf_stream, a.ssf_ev, 0);
+        if (e2 != hipSuccess) return (int)e2;
+        ss = a.ssf_stream;
+    }
+    if (p.ssf == kFinLut) {
+        rc = g.n_gen <= 64 ? launch_ssf_lut<1, RV, RC>(g, p, a, num_cus, ss)
+                           : launch_ssf_lut<2, RV, RC>(g, p, a, num_cus, ss);
+    } else {
+        DevGraph gs = g;  // QD_SSF_SCAN_GATHER: no incremental local syndromes
+        if (p.ssf == kFinScanGather) gs.g_inv = nullptr;
+        rc = g.n_gen <= 64 ? launch_ssf_wave<1, RV, RC>(gs, a, num_cus, ss)
+                           : launch_ssf_wave<2, RV, RC>(gs, a, num_cus, ss);
+    }
+    record_ev(a, 2, ss);
     return rc;
 }
 
 template <typename T, int METHOD>
-static int dispatch_shape(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream) {
+static int dispatch_shape(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                          hipStream_t stream, bool* triaged) {
     const int rc = g.m_pad / 64, rv = g.n_pad / 64;
-#define QDEC_SHAPE(R, V, D) \
-    if (rc == R && rv == V && g.shape_drc == D) return launch_wave<T, METHOD, R, V, D>(g, a, num_cus, stream);
+#define QDEC_SHAPE(R, V, D)                     \
+    if (rc == R && rv == V && g.shape_drc == D) \
+        return launch_wave<T, METHOD, R, V, D>(g, p, a, num_cus, stream, triaged);
     QDEC_WAVE_SHAPES(QDEC_SHAPE)
 #undef QDEC_SHAPE
     return (int)hipErrorNotSupported;
@@ -1232,36 +1229,26 @@ static int launch_unpack_rows(const uint8_t* src, int64_t rows, int cols, uint8_
     return (int)hipGetLastError();
 }
 
-// A packed decode the triage can read directly: a lean min-sum launch on a wave
-// graph that takes the two-pass path (launch_wave / launch_bp_wave's choice).
-static bool packed_two_pass(const DevGraph& g, int method, const DecodeArgs& a0) {
-    if (method != 1 || !g.wave || !wave_kernel_supports(g)) return false;
-    DecodeArgs a = a0;
-    const bool ssf_wave = g.n_gen <= 128 && g.g_lc8;
-    a.q_packed = a.ssf && ssf_wave ? 1 : 0;
-    if (a.ssf) return ssf_wave && g.k <= g.n_pad && compact_launch(g, a, true);
-    return compact_launch(g, a, false);
-}
-
-int launch_decode(const DevGraph& g, int method, int precision, const DecodeArgs& a0, int num_cus,
-                  hipStream_t stream, void* scratch, size_t scratch_bytes) {
+int launch_decode(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a0, int num_cus, hipStream_t stream,
+                  void* scratch, size_t scratch_bytes, bool* triaged) {
     last_launch_names() = LaunchNames{};
+    *triaged = false;
     if (a0.B <= 0) return 0;
     DecodeArgs a = a0;
-    if (a.in_packed && !packed_two_pass(g, method, a)) {
-        // every other path reads byte rows: expand the inputs first
+    if (p.expand_packed) {
+        // byte rows for every reader but the triage's packed branch
         if (!a.unpack_buf) return (int)hipErrorInvalidValue;
         uint8_t* u = a.unpack_buf;
         int rc = 0;
         if (a.syn) {
             rc = launch_unpack_rows(a.syn, a.B, g.m, u, num_cus, stream);
             a.syn = u;
-            u += (size_t)a.B * g.m;
+            u += unpack_region(a.B, g.m);
         }
         if (rc == 0 && a.base) {
             rc = launch_unpack_rows(a.base, a.B, g.n_data, u, num_cus, stream);
             a.base = u;
-            u += (size_t)a.B * g.n_data;
+            u += unpack_region(a.B, g.n_data);
         }
         if (rc == 0 && a.readout) {
             rc = launch_unpack_rows(a.readout, a.B, g.n_data, u, num_cus, stream);
@@ -1270,13 +1257,12 @@ int launch_decode(const DevGraph& g, int method, int precision, const DecodeArgs
         if (rc != 0) return rc;
         a.in_packed = 0;
     }
-    if (!g.wave || !wave_kernel_supports(g))
-        return launch_decode_block(g, method, precision, a, num_cus, stream, scratch, scratch_bytes);
-    if (precision == 1)
-        return method == 1 ? dispatch_shape<float, 1>(g, a, num_cus, stream)
-                           : dispatch_shape<float, 0>(g, a, num_cus, stream);
-    return method == 1 ? dispatch_shape<double, 1>(g, a, num_cus, stream)
-                       : dispatch_shape<double, 0>(g, a, num_cus, stream);
+    if (p.bp >= kBpGroup) return launch_decode_block(g, p, a, num_cus, stream, scratch, scratch_bytes);
+    if (p.precision == 1)
+        return p.method == 1 ? dispatch_shape<float, 1>(g, p, a, num_cus, stream, triaged)
+                             : dispatch_shape<float, 0>(g, p, a, num_cus, stream, triaged);
+    return p.method == 1 ? dispatch_shape<double, 1>(g, p, a, num_cus, stream, triaged)
+                         : dispatch_shape<double, 0>(g, p, a, num_cus, stream, triaged);
 }
 
 #ifdef QDEC_STAMPS

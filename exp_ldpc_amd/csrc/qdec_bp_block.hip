@@ -1947,54 +1947,29 @@ extern "C" __attribute__((visibility("default"))) int qd_dev_read_stamps_block(u
 #endif
 
 // ---------------------------------------------------------------- launcher
-template <typename K, typename P>
-static int launch_block(K kern, size_t lds, int64_t work, int num_cus, hipStream_t stream, int cap_per_cu,
-                        const DevGraph& g, const DecodeArgs& a, P* extra0, int extra1) {
-    int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, lds);
-    if (e != hipSuccess) return (int)e;
-    if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-    if (cap_per_cu > 0 && per_cu > cap_per_cu) per_cu = cap_per_cu;
-    long long grid = (long long)num_cus * per_cu;
-    if (grid > work) grid = work;
-    if (grid <= 0) return 0;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, stream, g, a, extra0, extra1);
-    return (int)hipGetLastError();
-}
-
-template <typename K>
-static int launch_block2(K kern, size_t lds, int64_t work, int num_cus, hipStream_t stream, const DevGraph& g,
-                         const DecodeArgs& a, unsigned char* gstate = nullptr, int max_per_cu = 0) {
-    int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, lds);
-    if (e != hipSuccess) return (int)e;
-    if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-    if (max_per_cu > 0 && per_cu > max_per_cu) per_cu = max_per_cu;
-    long long grid = (long long)num_cus * per_cu;
-    if (grid > work) grid = work;
-    if (grid <= 0) return 0;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, stream, g, a, gstate);
-    return (int)hipGetLastError();
-}
-
 // SSF + finalize of queued shots whose state fits LDS: the incremental kernel
 // when the inverse table exists (QD_OPT_SSF_INC = 0 selects the re-scanning one).
-static int launch_ssf_fin(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream) {
-    const size_t lds = ssf_inc_lds(g);
-    if (a.ssf && g.g_iptr && g.n_gen <= 8192 && lds <= 160 * 1024 && g.opt_ssf_inc) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ssf_inc_block_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        int per_cu = 0;
-        hipError_t e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ssf_inc_block_kernel, kBlock, lds);
-        if (e2 != hipSuccess) return (int)e2;
-        if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-        const long long grid = std::min<long long>((long long)num_cus * per_cu, a.B);
-        if (grid <= 0) return 0;
-        hipLaunchKernelGGL(ssf_inc_block_kernel, dim3((unsigned)grid), dim3(kBlock), lds, stream, g, a);
-        return (int)hipGetLastError();
+int ssf_fin_path(const DevGraph& g, const DecodeArgs& a) {
+    return a.ssf && g.g_iptr && g.n_gen <= 8192 && ssf_inc_lds(g) <= 160 * 1024 && g.opt_ssf_inc ? kFinIncBlock
+                                                                                                : kFinBlockLds;
+}
+
+// the plan's SSF / finalize kernel; fin_state: the HBM shot state of kFinBlockHbm
+static int launch_ssf_fin(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                          hipStream_t stream, unsigned char* fin_state = nullptr) {
+    switch (p.ssf) {
+        case kFinNone: return 0;
+        case kFinIncBlock:
+            return launch_resident(ssf_inc_block_kernel, kBlock, ssf_inc_lds(g), num_cus, a.B, stream, {}, g, a);
+        case kFinBlockLds:
+            return launch_resident(ssf_block_kernel, kBlock, (block_small_lds(g) + 15) / 16 * 16, num_cus, a.B, stream,
+                                   {}, g, a, (unsigned char*)nullptr);
+        case kFinBlockHbm:
+            if (!fin_state) return (int)hipErrorInvalidValue;
+            return launch_resident(ssf_block_kernel, kBlock, kCtrl, num_cus, a.B, stream, GridRule{kFinPerCu}, g, a,
+                                   fin_state);
     }
-    return launch_block2(ssf_block_kernel, (block_small_lds(g) + 15) / 16 * 16, a.B, num_cus, stream, g, a);
+    return (int)hipErrorNotSupported;
 }
 
 constexpr size_t kLdsMsgLimit = 64 * 1024;  // messages in LDS up to this (2 workgroups per CU)
@@ -2010,21 +1985,24 @@ inline int block_placement(const DevGraph& g, size_t tsz) {
     return small <= kLdsMsgLimit ? 2 : 0;
 }
 
+// HBM shot state of the SSF/finalize workgroups (kFinBlockHbm: kFinPerCu
+// workgroups per CU), at the tail of the message scratch
+static size_t fin_hbm_bytes(const DevGraph& g, const DecodePlan& p, int num_cus) {
+    return p.ssf == kFinBlockHbm ? (size_t)num_cus * kFinPerCu * block_state_stride(g) : 0;
+}
+
 template <typename T, int METHOD>
-static int launch_block_typed(const DevGraph& g, const DecodeArgs& a0, int num_cus, hipStream_t stream, void* scratch,
-                              size_t scratch_bytes) {
+static int launch_block_typed(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a0, int num_cus,
+                              hipStream_t stream, void* scratch, size_t scratch_bytes) {
     const size_t msg = ((size_t)2 * g.E * sizeof(T) + 15) / 16 * 16;
     const size_t small = (block_small_lds(g) + 15) / 16 * 16;
-    const int placement = block_placement(g, sizeof(T));
+    const int placement = p.placement;
     // placement 0: control area + the hard-decision bits of the unrolled kernel
     const size_t lds = (placement & 2) ? small + ((placement & 1) ? msg : 0) : kCtrl + (size_t)g.n_pad / 8;
     int cap = 0;
     T* gs = nullptr;
     DecodeArgs a = a0;
-    // placement 0 with SSF: the SSF/finalize workgroups keep their shot state in
-    // HBM too, in the scratch tail (kFinPerCu workgroups per CU)
-    const bool fin_hbm = a0.ssf && placement == 0;
-    const size_t fin_bytes = fin_hbm ? (size_t)num_cus * kFinPerCu * block_state_stride(g) : 0;
+    const size_t fin_bytes = fin_hbm_bytes(g, p, num_cus);
     if (placement != 3) {
         // scratch = header (dynamic shot counter) + per-workgroup slices in HBM
         const size_t per_wg = block_slice_bytes(g, sizeof(T), placement);
@@ -2050,12 +2028,13 @@ static int launch_block_typed(const DevGraph& g, const DecodeArgs& a0, int num_c
     // graphs with row degree <= 16 and column degree <= 8: unrolled loops
     const bool unr = g.max_rdeg <= 16 && g.max_cdeg <= 8;
     constexpr int UR = 16, UC = 8;
-    if (!a.ssf) {
+    const GridRule rule{cap};
+    if (p.ssf == kFinNone) {
         record_ev(a, 0, stream);
-        const int rc = unr ? launch_block(bp_block_kernel<T, METHOD, false, UR, UC>, lds, a.B, num_cus, stream, cap, g, a,
-                                          gs, placement)
-                           : launch_block(bp_block_kernel<T, METHOD, false>, lds, a.B, num_cus, stream, cap, g, a, gs,
-                                          placement);
+        const int rc = unr ? launch_resident(bp_block_kernel<T, METHOD, false, UR, UC>, kBlock, lds, num_cus, a.B,
+                                             stream, rule, g, a, gs, placement)
+                           : launch_resident(bp_block_kernel<T, METHOD, false>, kBlock, lds, num_cus, a.B, stream, rule,
+                                             g, a, gs, placement);
         record_ev(a, 1, stream);
         record_ev(a, 2, stream);
         return rc;
@@ -2064,14 +2043,14 @@ static int launch_block_typed(const DevGraph& g, const DecodeArgs& a0, int num_c
     hipError_t e = hipMemsetAsync(a.q_count, 0, sizeof(int32_t), stream);
     if (e != hipSuccess) return (int)e;
     record_ev(a, 0, stream);
-    int rc = unr ? launch_block(bp_block_kernel<T, METHOD, true, UR, UC>, lds, a.B, num_cus, stream, cap, g, a, gs,
-                                placement)
-                 : launch_block(bp_block_kernel<T, METHOD, true>, lds, a.B, num_cus, stream, cap, g, a, gs, placement);
+    int rc = unr ? launch_resident(bp_block_kernel<T, METHOD, true, UR, UC>, kBlock, lds, num_cus, a.B, stream, rule,
+                                   g, a, gs, placement)
+                 : launch_resident(bp_block_kernel<T, METHOD, true>, kBlock, lds, num_cus, a.B, stream, rule, g, a, gs,
+                                   placement);
     record_ev(a, 1, stream);
     if (rc != 0) return rc;
-    rc = fin_hbm ? launch_block2(ssf_block_kernel, kCtrl, a.B, num_cus, stream, g, a,
-                                 static_cast<unsigned char*>(scratch) + (scratch_bytes - fin_bytes), kFinPerCu)
-                 : launch_ssf_fin(g, a, num_cus, stream);
+    rc = launch_ssf_fin(g, p, a, num_cus, stream,
+                        fin_bytes ? static_cast<unsigned char*>(scratch) + (scratch_bytes - fin_bytes) : nullptr);
     record_ev(a, 2, stream);
     return rc;
 }
@@ -2081,38 +2060,34 @@ static int launch_block_typed(const DevGraph& g, const DecodeArgs& a0, int num_c
 // them on any graph they can hold (also those whose messages fit the small-graph
 // LDS budget); by default they take the min-sum graphs whose messages would go
 // to HBM (f32: edge slots <= 160 KB; f64: n <= 10240 and the check states <= 160 KB).
-bool lds_kernel_applies(const DevGraph& g, int method, int precision, const DecodeArgs& a) {
-    if (method != 1 || !g.ml_etab || (precision == 0 && (!g.m64_etab || !g.m64_check))) return false;
-    if (!a.syn || a.syn_flags || a.llr_out || !a.wave_ctr) return false;
+static bool lds_kernel_applies(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a) {
+    const int precision = p.precision;
+    if (p.method != 1 || !g.ml_etab || (precision == 0 && (!g.m64_etab || !g.m64_check))) return false;
+    if (!a.syn || a.syn_flags || a.llr_out) return false;
     if (precision == 0) {  // bp_ms_lds64_kernel (automatic: graphs whose messages would go to HBM)
         if (g.n > 10 * kM64Threads || g.m <= 0 || g.m > kM64Nch * kM64Threads || a.max_iter < 1) return false;
-        if (m64_lds_bytes(g) > 160 * 1024 || block_placement(g, 8) == 0) return false;
+        if (m64_lds_bytes(g) > 160 * 1024 || p.placement == 0) return false;
         if (g.opt_lds_kernel == 0) return false;
-        return g.opt_lds_kernel == 1 || block_placement(g, 8) != 3;
+        return g.opt_lds_kernel == 1 || p.placement != 3;
     }
     if (precision != 1) return false;
     if (g.n > 16 * kMlThreads || g.m <= 0 || g.m > kMlNch * kMlThreads || a.max_iter < 1 ||
         ml_lds_bytes(g) > 160 * 1024)
         return false;
-    if (block_placement(g, 4) == 0) return false;  // the SSF/finalize state would not fit LDS
+    if (p.placement == 0) return false;  // the SSF/finalize state would not fit LDS
     if (g.opt_lds_kernel == 0) return false;
     if (g.opt_lds_kernel == 1) return true;
-    return block_placement(g, 4) != 3;
+    return p.placement != 3;
 }
 
 template <int VPT>
-static int launch_lds_typed(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream, float* img,
-                            size_t img_bytes) {
+static int launch_lds_typed(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                            hipStream_t stream, float* img, size_t img_bytes) {
     const size_t lds = ml_lds_bytes(g);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bp_ms_lds_kernel<VPT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    long long grid = 0;
+    hipError_t e = resident_grid(bp_ms_lds_kernel<VPT>, kMlThreads, lds, num_cus, a.B, &grid);
     if (e != hipSuccess) return (int)e;
-    int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bp_ms_lds_kernel<VPT>, kMlThreads, lds);
-    if (e != hipSuccess) return (int)e;
-    if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
     if (!img || img_bytes < ml_image_bytes(g)) return (int)hipErrorInvalidValue;
-    const long long grid = std::min<long long>((long long)num_cus * per_cu, a.B);
     e = hipMemsetAsync(a.wave_ctr, 0, sizeof(unsigned long long), stream);  // shot counter
     if (e != hipSuccess) return (int)e;
     const float* prior = reinterpret_cast<const float*>(g.prior[1][1]);
@@ -2127,25 +2102,18 @@ static int launch_lds_typed(const DevGraph& g, const DecodeArgs& a, int num_cus,
     const hipError_t le = hipGetLastError();
     record_ev(a, 1, stream);
     if (le != hipSuccess) return (int)le;
-    const bool fin_hbm = block_placement(g, 4) == 0;
-    const int rc = fin_hbm ? (int)hipErrorNotSupported
-                           : launch_ssf_fin(g, a, num_cus, stream);
+    const int rc = launch_ssf_fin(g, p, a, num_cus, stream);
     record_ev(a, 2, stream);
     return rc;
 }
 
 template <int VPT, int D3R>
-static int launch_lds64_typed(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream,
-                              unsigned long long* img, size_t img_bytes) {
+static int launch_lds64_typed(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                              hipStream_t stream, unsigned long long* img, size_t img_bytes) {
     const size_t lds = m64_lds_bytes(g);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bp_ms_lds64_kernel<VPT, D3R>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    long long grid = 0;
+    hipError_t e = resident_grid(bp_ms_lds64_kernel<VPT, D3R>, kM64Threads, lds, num_cus, a.B, &grid);
     if (e != hipSuccess) return (int)e;
-    int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bp_ms_lds64_kernel<VPT, D3R>, kM64Threads, lds);
-    if (e != hipSuccess) return (int)e;
-    if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-    const long long grid = std::min<long long>((long long)num_cus * per_cu, a.B);
     e = hipMemsetAsync(a.wave_ctr, 0, sizeof(unsigned long long), stream);  // shot counter
     if (e != hipSuccess) return (int)e;
     if (!img || img_bytes < m64_image_bytes(g)) return (int)hipErrorInvalidValue;
@@ -2159,33 +2127,33 @@ static int launch_lds64_typed(const DevGraph& g, const DecodeArgs& a, int num_cu
     const hipError_t le = hipGetLastError();
     record_ev(a, 1, stream);
     if (le != hipSuccess) return (int)le;
-    const int rc = launch_ssf_fin(g, a, num_cus, stream);
+    const int rc = launch_ssf_fin(g, p, a, num_cus, stream);
     record_ev(a, 2, stream);
     return rc;
 }
 
-static int launch_lds(const DevGraph& g, int precision, const DecodeArgs& a, int num_cus, hipStream_t stream,
+static int launch_lds(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus, hipStream_t stream,
                       void* scratch, size_t scratch_bytes) {
     unsigned long long* img = reinterpret_cast<unsigned long long*>(scratch);  // f64: iteration 1's states
-    if (!a.q_count || !a.q_idx || !a.q_x || !a.q_r) return (int)hipErrorInvalidValue;
-    if (precision == 0) {
+    if (!a.q_count || !a.q_idx || !a.q_x || !a.q_r || !a.wave_ctr) return (int)hipErrorInvalidValue;
+    if (p.precision == 0) {
         // the largest instantiated D3R <= the graph's (leading rounds of degree <= 3)
         const int vpt = (g.n + kM64Threads - 1) / kM64Threads, d3r = g.m64_d3r;
-        if (vpt <= 4) return launch_lds64_typed<4, 0>(g, a, num_cus, stream, img, scratch_bytes);
+        if (vpt <= 4) return launch_lds64_typed<4, 0>(g, p, a, num_cus, stream, img, scratch_bytes);
         if (vpt <= 8)
-            return d3r >= 4 ? launch_lds64_typed<8, 4>(g, a, num_cus, stream, img, scratch_bytes)
-                            : launch_lds64_typed<8, 0>(g, a, num_cus, stream, img, scratch_bytes);
-        if (d3r >= 6) return launch_lds64_typed<10, 6>(g, a, num_cus, stream, img, scratch_bytes);
-        if (d3r >= 3) return launch_lds64_typed<10, 3>(g, a, num_cus, stream, img, scratch_bytes);
-        return launch_lds64_typed<10, 0>(g, a, num_cus, stream, img, scratch_bytes);
+            return d3r >= 4 ? launch_lds64_typed<8, 4>(g, p, a, num_cus, stream, img, scratch_bytes)
+                            : launch_lds64_typed<8, 0>(g, p, a, num_cus, stream, img, scratch_bytes);
+        if (d3r >= 6) return launch_lds64_typed<10, 6>(g, p, a, num_cus, stream, img, scratch_bytes);
+        if (d3r >= 3) return launch_lds64_typed<10, 3>(g, p, a, num_cus, stream, img, scratch_bytes);
+        return launch_lds64_typed<10, 0>(g, p, a, num_cus, stream, img, scratch_bytes);
     }
     float* fimg = reinterpret_cast<float*>(scratch);  // f32: iteration 1's c2v rows
     const int vpt = (g.n + kMlThreads - 1) / kMlThreads;
-    if (vpt <= 4) return launch_lds_typed<4>(g, a, num_cus, stream, fimg, scratch_bytes);
-    if (vpt <= 8) return launch_lds_typed<8>(g, a, num_cus, stream, fimg, scratch_bytes);
-    if (vpt <= 10) return launch_lds_typed<10>(g, a, num_cus, stream, fimg, scratch_bytes);
-    if (vpt <= 12) return launch_lds_typed<12>(g, a, num_cus, stream, fimg, scratch_bytes);
-    return launch_lds_typed<16>(g, a, num_cus, stream, fimg, scratch_bytes);
+    if (vpt <= 4) return launch_lds_typed<4>(g, p, a, num_cus, stream, fimg, scratch_bytes);
+    if (vpt <= 8) return launch_lds_typed<8>(g, p, a, num_cus, stream, fimg, scratch_bytes);
+    if (vpt <= 10) return launch_lds_typed<10>(g, p, a, num_cus, stream, fimg, scratch_bytes);
+    if (vpt <= 12) return launch_lds_typed<12>(g, p, a, num_cus, stream, fimg, scratch_bytes);
+    return launch_lds_typed<16>(g, p, a, num_cus, stream, fimg, scratch_bytes);
 }
 
 // ---------------------------------------------------------------- slot-group launch
@@ -2244,34 +2212,27 @@ static int64_t group_count(const DevGraph& g, int method, size_t tsz, int num_cu
 // with HBM message slices), =1 forces it on any graph within those degrees.
 // For fp32 min-sum graphs the LDS-resident kernel (bp_ms_lds_kernel) keeps
 // precedence unless the group kernel is forced.
-bool group_kernel_applies(const DevGraph& g, int method, int precision, const DecodeArgs& a) {
+static bool group_kernel_applies(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a) {
     if (g.max_rdeg > 16 || g.max_cdeg > 8 || !a.syn || a.syn_flags) return false;
-    (void)method;
     if (g.opt_group_kernel == 0) return false;
     if (g.opt_group_kernel == 1) return true;
-    return block_placement(g, precision == 1 ? 4 : 8) != 3;
+    return p.placement != 3;
 }
 
 template <typename T, int METHOD, int DR, int DC>
-static int launch_group_typed(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream, void* scratch,
-                              size_t scratch_bytes) {
+static int launch_group_typed(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                              hipStream_t stream, void* scratch, size_t scratch_bytes) {
     const size_t gb = group_layout(g, sizeof(T)).total;
-    // tail of the scratch: HBM shot state of the SSF/finalize workgroups when it
-    // does not fit LDS (kFinPerCu workgroups per CU)
-    const bool fin_hbm = a.ssf && block_placement(g, sizeof(T)) == 0;
-    const size_t fin_bytes = fin_hbm ? (size_t)num_cus * kFinPerCu * block_state_stride(g) : 0;
+    const size_t fin_bytes = fin_hbm_bytes(g, p, num_cus);
     if (!scratch || scratch_bytes < fin_bytes + kGrpHeader + gb) return (int)hipErrorOutOfMemory;
     unsigned char* base = static_cast<unsigned char*>(scratch);
-    unsigned char* fin_state = fin_hbm ? base + (scratch_bytes - fin_bytes) : nullptr;
+    unsigned char* fin_state = fin_bytes ? base + (scratch_bytes - fin_bytes) : nullptr;
     const int64_t max_groups = (int64_t)((scratch_bytes - fin_bytes - kGrpHeader) / gb);
-    int per_cu = 0;
     constexpr int kGrpThreads = 64 * grp_waves<T>();
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bp_group_kernel<T, METHOD, DR, DC>,
-                                                                kGrpThreads, 0);
+    long long grid = 0;
+    hipError_t e = resident_grid(bp_group_kernel<T, METHOD, DR, DC>, kGrpThreads, 0, num_cus,
+                                 std::min<int64_t>(max_groups, group_count(g, METHOD, sizeof(T), num_cus, a.B)), &grid);
     if (e != hipSuccess) return (int)e;
-    if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-    int64_t grid = std::min<int64_t>((int64_t)num_cus * per_cu, max_groups);
-    grid = std::min<int64_t>(grid, group_count(g, METHOD, sizeof(T), num_cus, a.B));
     if (grid <= 0) return (int)hipErrorOutOfMemory;
     e = hipMemsetAsync(base, 0, sizeof(unsigned long long), stream);  // shot counter
     if (e != hipSuccess) return (int)e;
@@ -2289,77 +2250,84 @@ static int launch_group_typed(const DevGraph& g, const DecodeArgs& a, int num_cu
     const hipError_t le = hipGetLastError();
     record_ev(a, 1, stream);
     if (le != hipSuccess) return (int)le;
-    int rc = 0;
-    if (a.ssf)
-        rc = fin_hbm ? launch_block2(ssf_block_kernel, kCtrl, a.B, num_cus, stream, g, a, fin_state, kFinPerCu)
-                     : launch_ssf_fin(g, a, num_cus, stream);
+    const int rc = launch_ssf_fin(g, p, a, num_cus, stream, fin_state);
     record_ev(a, 2, stream);
     return rc;
 }
 
 template <typename T, int METHOD>
-static int launch_group_shape(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream, void* scratch,
-                              size_t scratch_bytes) {
+static int launch_group_shape(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                              hipStream_t stream, void* scratch, size_t scratch_bytes) {
     const bool r8 = g.max_rdeg <= 8, c4 = g.max_cdeg <= 4;
-    if (r8) return c4 ? launch_group_typed<T, METHOD, 8, 4>(g, a, num_cus, stream, scratch, scratch_bytes)
-                      : launch_group_typed<T, METHOD, 8, 8>(g, a, num_cus, stream, scratch, scratch_bytes);
-    return c4 ? launch_group_typed<T, METHOD, 16, 4>(g, a, num_cus, stream, scratch, scratch_bytes)
-              : launch_group_typed<T, METHOD, 16, 8>(g, a, num_cus, stream, scratch, scratch_bytes);
+    if (r8) return c4 ? launch_group_typed<T, METHOD, 8, 4>(g, p, a, num_cus, stream, scratch, scratch_bytes)
+                      : launch_group_typed<T, METHOD, 8, 8>(g, p, a, num_cus, stream, scratch, scratch_bytes);
+    return c4 ? launch_group_typed<T, METHOD, 16, 4>(g, p, a, num_cus, stream, scratch, scratch_bytes)
+              : launch_group_typed<T, METHOD, 16, 8>(g, p, a, num_cus, stream, scratch, scratch_bytes);
 }
 
-size_t block_scratch_bytes(const DevGraph& g, int method, int precision, int num_cus, const DecodeArgs& a) {
-    const size_t tsz = precision == 1 ? 4 : 8;
-    if (group_kernel_applies(g, method, precision, a) && !(lds_kernel_applies(g, method, precision, a) && g.opt_group_kernel != 1)) {
-        const size_t fin = (a.ssf && block_placement(g, tsz) == 0) ? (size_t)num_cus * kFinPerCu * block_state_stride(g)
-                                                                  : 0;
-        return kGrpHeader + (size_t)group_count(g, method, tsz, num_cus, a.B) * group_layout(g, tsz).total + fin;
+// The workgroup half of plan_decode.  The slot-group kernel has precedence over
+// the workgroup kernel; the LDS-resident kernels over both unless the group
+// kernel is forced.  The LDS-resident kernels finalize through the queue even
+// without SSF.
+void plan_decode_block(const DevGraph& g, const DecodeArgs& a, DecodePlan& p) {
+    p.placement = block_placement(g, p.precision == 1 ? 4 : 8);
+    const bool lds = lds_kernel_applies(g, p, a);
+    const bool group = group_kernel_applies(g, p, a) && !(lds && g.opt_group_kernel != 1);
+    p.bp = group ? kBpGroup : lds ? kBpLds : kBpBlock;
+    p.ssf = !a.ssf && p.bp != kBpLds ? kFinNone : p.placement == 0 ? kFinBlockHbm : ssf_fin_path(g, a);
+    p.expand_packed = a.in_packed != 0;
+    p.need_scratch = p.bp != kBpBlock || p.placement != 3;
+}
+
+size_t block_scratch_bytes(const DevGraph& g, const DecodePlan& p, int num_cus, const DecodeArgs& a) {
+    const size_t tsz = p.precision == 1 ? 4 : 8;
+    const size_t fin = fin_hbm_bytes(g, p, num_cus);
+    switch (p.bp) {
+        case kBpGroup:
+            return kGrpHeader + (size_t)group_count(g, p.method, tsz, num_cus, a.B) * group_layout(g, tsz).total + fin;
+        case kBpLds:
+            // iteration 1's image (f64: check states, m64_init_kernel; f32: c2v rows, ml_init_*_kernel)
+            return p.precision == 0 ? m64_image_bytes(g) : ml_image_bytes(g);
+        case kBpBlock:
+            if (p.placement == 3) return 0;
+            // shot-counter header + up to 4 workgroup slices per CU (+ the SSF/finalize
+            // shot state when it lives in HBM)
+            return kGrpHeader + (size_t)num_cus * 4 * block_slice_bytes(g, tsz, p.placement) + fin;
     }
-    // LDS-resident kernels: iteration 1's image (f64: check states, m64_init_kernel;
-    // f32: c2v rows, ml_init_*_kernel)
-    if (lds_kernel_applies(g, method, precision, a)) return precision == 0 ? m64_image_bytes(g) : ml_image_bytes(g);
-    const int placement = block_placement(g, tsz);
-    if (placement == 3) return 0;
-    // shot-counter header + up to 4 workgroup slices per CU (+ the SSF/finalize
-    // shot state when it lives in HBM)
-    const size_t fin = (a.ssf && placement == 0) ? (size_t)num_cus * kFinPerCu * block_state_stride(g) : 0;
-    return kGrpHeader + (size_t)num_cus * 4 * block_slice_bytes(g, tsz, placement) + fin;
+    return 0;  // wave graphs
 }
 
 // The smallest scratch a launch can run with (one slot group, or one workgroup
 // slice per CU); block_scratch_bytes' figure may be cut down to it when the
 // allocation fails (fewer groups / slices in flight, same results).
-size_t block_scratch_floor(const DevGraph& g, int method, int precision, int num_cus, const DecodeArgs& a) {
-    const size_t full = block_scratch_bytes(g, method, precision, num_cus, a);
-    if (full == 0) return 0;
-    const size_t tsz = precision == 1 ? 4 : 8;
-    const size_t fin = (a.ssf && block_placement(g, tsz) == 0) ? (size_t)num_cus * kFinPerCu * block_state_stride(g) : 0;
-    if (group_kernel_applies(g, method, precision, a) && !(lds_kernel_applies(g, method, precision, a) && g.opt_group_kernel != 1))
-        return std::min(full, kGrpHeader + group_layout(g, tsz).total + fin);
-    return full;  // workgroup slices: the launch needs its per-CU slices
+size_t block_scratch_floor(const DevGraph& g, const DecodePlan& p, int num_cus, const DecodeArgs& a) {
+    const size_t full = block_scratch_bytes(g, p, num_cus, a);
+    if (p.bp != kBpGroup) return full;  // workgroup slices: the launch needs its per-CU slices
+    const size_t tsz = p.precision == 1 ? 4 : 8;
+    return std::min(full, kGrpHeader + group_layout(g, tsz).total + fin_hbm_bytes(g, p, num_cus));
 }
 
-int launch_decode_block(const DevGraph& g, int method, int precision, const DecodeArgs& a, int num_cus,
+int launch_decode_block(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
                         hipStream_t stream, void* scratch, size_t scratch_bytes) {
     if (a.B <= 0) return 0;
     if (a.ssf && g.n_gen <= 0) return (int)hipErrorInvalidValue;
-    const bool lds = lds_kernel_applies(g, method, precision, a);
-    if (group_kernel_applies(g, method, precision, a) && !(lds && g.opt_group_kernel != 1)) {
-        if (precision == 1)
-            return method == 1 ? launch_group_shape<float, 1>(g, a, num_cus, stream, scratch, scratch_bytes)
-                               : launch_group_shape<float, 0>(g, a, num_cus, stream, scratch, scratch_bytes);
-        return method == 1 ? launch_group_shape<double, 1>(g, a, num_cus, stream, scratch, scratch_bytes)
-                           : launch_group_shape<double, 0>(g, a, num_cus, stream, scratch, scratch_bytes);
+#define QDEC_BLOCK_TYPES(F)                                                                             \
+    if (p.precision == 1)                                                                               \
+        return p.method == 1 ? F<float, 1>(g, p, a, num_cus, stream, scratch, scratch_bytes)            \
+                             : F<float, 0>(g, p, a, num_cus, stream, scratch, scratch_bytes);           \
+    return p.method == 1 ? F<double, 1>(g, p, a, num_cus, stream, scratch, scratch_bytes)               \
+                         : F<double, 0>(g, p, a, num_cus, stream, scratch, scratch_bytes);
+    switch (p.bp) {
+        case kBpGroup: QDEC_BLOCK_TYPES(launch_group_shape)
+        case kBpLds: return launch_lds(g, p, a, num_cus, stream, scratch, scratch_bytes);
+        case kBpBlock: QDEC_BLOCK_TYPES(launch_block_typed)
     }
-    if (lds) return launch_lds(g, precision, a, num_cus, stream, scratch, scratch_bytes);
-    if (precision == 1)
-        return method == 1 ? launch_block_typed<float, 1>(g, a, num_cus, stream, scratch, scratch_bytes)
-                           : launch_block_typed<float, 0>(g, a, num_cus, stream, scratch, scratch_bytes);
-    return method == 1 ? launch_block_typed<double, 1>(g, a, num_cus, stream, scratch, scratch_bytes)
-                       : launch_block_typed<double, 0>(g, a, num_cus, stream, scratch, scratch_bytes);
+#undef QDEC_BLOCK_TYPES
+    return (int)hipErrorNotSupported;
 }
 
-int launch_ssf_block(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream) {
-    return launch_ssf_fin(g, a, num_cus, stream);
+int launch_ssf_block(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus, hipStream_t stream) {
+    return launch_ssf_fin(g, p, a, num_cus, stream);
 }
 
 }  // namespace qdec

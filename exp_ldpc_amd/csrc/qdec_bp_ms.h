@@ -916,8 +916,11 @@ __global__ __launch_bounds__(64, 1) void ms_triage_kernel(DevGraph g, DecodeArgs
     uint64_t sw[RC];
     uint64_t rw[NWD];
     if constexpr (PK) {
-        // one row of u64 words per shot (RC = ceil(m / 64), NWD = ceil(n_data / 64)
-        // on wave graphs): lane-strided loads, padding bits cleared
+        // one row of u64 words per shot: lane-strided loads, padding bits cleared.
+        // Precondition (plan_decode, expand_packed): RC == ceil(m / 64), the row
+        // length the ABI, the sampler and pack_rows write.  A wave shape may have
+        // more check rounds than that (m <= 64 on (2, 3, *), m <= 128 on
+        // (4, 9, 8)); those decodes expand their rows and take the byte branch.
         const uint64_t* sp = reinterpret_cast<const uint64_t*>(a.syn) + min(shot, a.B - 1) * RC;
 #pragma unroll
         for (int rc = 0; rc < RC; ++rc) {

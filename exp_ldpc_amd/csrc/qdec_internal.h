@@ -152,16 +152,67 @@ inline std::string kernel_name(const char* base, A... args) {
     } while (0)
 
 
+// ---------------------------------------------------------------- launch plan
+// Everything a decode decides before its first launch, decided once
+// (plan_decode) and read by the buffer attachment (qdec_abi.cpp) and by the
+// launchers.  DESIGN §3 has the decision table.
+enum BpPath {
+    kBpWave = 0,     // bp_wave_kernel: wave graph, message arrays (product-sum)
+    kBpMsWave = 1,   // bp_ms_wave_kernel: wave graph, min-sum, one pass
+    kBpTwoPass = 2,  // ms_triage_kernel + bp_ms_cmp_kernel: wave graph, lean min-sum
+    kBpGroup = 3,    // bp_group_kernel: slot groups, messages in HBM
+    kBpLds = 4,      // bp_ms_lds_kernel (f32) / bp_ms_lds64_kernel (f64)
+    kBpBlock = 5,    // bp_block_kernel, state placed by `placement`
+};
+enum SsfPath {
+    kFinNone = 0,        // the BP kernel finalizes every shot itself
+    kFinFused = 1,       // SSF inside bp_ms_cmp_kernel (FUSE = 1 / 2)
+    kFinLut = 2,         // ssf_lut_kernel
+    kFinScan = 3,        // ssf_wave_kernel
+    kFinScanGather = 4,  // ssf_wave_kernel without the inverse table
+    kFinScanNoSplit = 5, // ssf_wave_kernel, one lane per generator
+    kFinIncBlock = 6,    // ssf_inc_block_kernel
+    kFinBlockLds = 7,    // ssf_block_kernel, shot state in LDS
+    kFinBlockHbm = 8,    // ssf_block_kernel, shot state in the scratch tail
+};
+struct DecodePlan {
+    int method, precision;
+    int bp;              // BpPath
+    int ssf;             // SsfPath
+    int placement;       // kBpBlock's block_placement (also decides kFinBlockHbm); 3 on wave graphs
+    bool two_pass;       // bp == kBpTwoPass
+    bool lean;           // wave min-sum: the LEAN instantiation of the one-pass kernel
+    bool defer;          // a queue consumer follows the BP kernel (ssf != kFinNone and != kFinFused)
+    int fuse;            // 0, or the generator words of the fused SSF (1: <= 64, 2: <= 128)
+    int q_packed, q_rpar;  // DecodeArgs' queue flags
+    bool ssf_lean;       // ssf_lut_kernel's LEAN instantiation
+    bool expand_packed;  // packed inputs go through unpack_rows_kernel first
+    // library-owned buffers the launch needs
+    bool need_queue, need_lists, need_unpack, need_scratch;
+};
+// Pure: reads the graph's fields and options and the caller's part of `a`
+// (which buffers are present, syn_flags, in_packed, ssf, max_iter, ms_scaling,
+// the alignment of syn / readout); no HIP call, so host-only graphs plan too.
+DecodePlan plan_decode(const DevGraph& g, int method, int precision, const DecodeArgs& a);
+// the workgroup half (qdec_bp_block.hip): graphs no wave shape holds
+void plan_decode_block(const DevGraph& g, const DecodeArgs& a, DecodePlan& p);
+// SSF + finalize of queued shots by a workgroup kernel with its state in LDS
+int ssf_fin_path(const DevGraph& g, const DecodeArgs& a);
+bool wave_kernel_supports(const DevGraph& g);
+// byte rows of expanded packed inputs: the regions of unpack_buf (16-B aligned,
+// so the byte-row triage can load them)
+inline size_t unpack_region(int64_t B, int cols) { return ((size_t)B * cols + 15) / 16 * 16; }
+
 // Launchers (qdec_bp.hip / qdec_sample.hip).  Return hipError_t as int.
-int launch_decode(const DevGraph& g, int method, int precision, const DecodeArgs& a,
-                  int num_cus, hipStream_t stream, void* scratch, size_t scratch_bytes);
-int launch_decode_block(const DevGraph& g, int method, int precision, const DecodeArgs& a, int num_cus,
+// *triaged: the two-pass path's triage was enqueued (it zeroed the other
+// counter set of the handle)
+int launch_decode(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus, hipStream_t stream,
+                  void* scratch, size_t scratch_bytes, bool* triaged);
+int launch_decode_block(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
                         hipStream_t stream, void* scratch, size_t scratch_bytes);
-int launch_ssf_block(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream);
-size_t block_scratch_bytes(const DevGraph& g, int method, int precision, int num_cus, const DecodeArgs& a);
-size_t block_scratch_floor(const DevGraph& g, int method, int precision, int num_cus, const DecodeArgs& a);
-bool group_kernel_applies(const DevGraph& g, int method, int precision, const DecodeArgs& a);
-bool lds_kernel_applies(const DevGraph& g, int method, int precision, const DecodeArgs& a);
+int launch_ssf_block(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus, hipStream_t stream);
+size_t block_scratch_bytes(const DevGraph& g, const DecodePlan& p, int num_cus, const DecodeArgs& a);
+size_t block_scratch_floor(const DevGraph& g, const DecodePlan& p, int num_cus, const DecodeArgs& a);
 int launch_sample_storage(const DevGraph& g, int rounds, uint32_t thr_data, uint32_t thr_meas,
                           uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
                           uint8_t* syn, uint8_t* readout, int num_cus, hipStream_t stream, bool packed = false);

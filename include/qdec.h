@@ -301,6 +301,43 @@ int qd_graph_ssf_tables(const qd_graph* g, int32_t* has_lut, int64_t* lut_bytes)
  * bytes per entry.  No reference counterpart. */
 int qd_graph_queue_layout(const qd_graph* g, int64_t B, int64_t* out);
 
+/* The launch plan of a decode of B shots with these parameters (diagnostic; also
+ * on host-only graphs): which kernels the call would run and which library
+ * buffers it would attach, decided by the same function the decode entry points
+ * use (plan_decode, qdec_internal.h).  `present`: the QD_PLAN_* bit of every
+ * optional buffer the call would pass, plus QD_PLAN_ROWS_ALIGNED when syn and
+ * readout meet the triage's alignment (16 B for byte rows, 8 B for packed
+ * rows; a packed decode refuses anything less).  out[8] = BP path (QD_BP_*),
+ * SSF / finalize path (QD_FIN_*), two_pass, expand_packed (packed inputs go
+ * through the byte expansion), fuse (0 / 1 / 2), q_rpar, placement of the
+ * workgroup kernel's state (3: messages and shot state in LDS, 2: messages in
+ * HBM, 0: both in HBM), buffers (bit 0 SSF queue, 1 compact lists, 2 unpack
+ * buffer, 3 HBM scratch).  No reference counterpart. */
+#define QD_PLAN_SYN 1u
+#define QD_PLAN_BASE 2u
+#define QD_PLAN_READOUT 4u
+#define QD_PLAN_X 8u
+#define QD_PLAN_CORR 16u
+#define QD_PLAN_LLR 32u
+#define QD_PLAN_FAIL 64u
+#define QD_PLAN_ROWS_ALIGNED 128u
+#define QD_BP_WAVE 0      /* bp_wave_kernel (product-sum on a wave graph) */
+#define QD_BP_MS_WAVE 1   /* bp_ms_wave_kernel */
+#define QD_BP_TWO_PASS 2  /* ms_triage_kernel + bp_ms_cmp_kernel */
+#define QD_BP_GROUP 3     /* bp_group_kernel */
+#define QD_BP_LDS 4       /* bp_ms_lds_kernel (f32) / bp_ms_lds64_kernel (f64) */
+#define QD_BP_BLOCK 5     /* bp_block_kernel */
+#define QD_FIN_NONE 0
+#define QD_FIN_FUSED 1          /* inside bp_ms_cmp_kernel */
+#define QD_FIN_LUT 2            /* ssf_lut_kernel */
+#define QD_FIN_SCAN 3           /* ssf_wave_kernel */
+#define QD_FIN_SCAN_GATHER 4
+#define QD_FIN_SCAN_NOSPLIT 5
+#define QD_FIN_INC_BLOCK 6      /* ssf_inc_block_kernel */
+#define QD_FIN_BLOCK_LDS 7      /* ssf_block_kernel, shot state in LDS */
+#define QD_FIN_BLOCK_HBM 8      /* ssf_block_kernel, shot state in HBM */
+int qd_graph_plan(const qd_graph* g, const qd_params* p, int64_t B, uint32_t present, int32_t* out);
+
 /* Copies of the triage's iteration-1 tables (host-only graphs): lut[n_pad]
  * (bit b = column j's hard decision after min-sum iteration 1 under syndrome
  * pattern b of its checks, in the kernels' precision and summation order) and

@@ -509,6 +509,122 @@ def test_host_only_queue_layout(code225):
         lib.qd_graph_destroy(h)
 
 
+PLAN_SYN, PLAN_BASE, PLAN_READOUT, PLAN_X, PLAN_CORR, PLAN_LLR, PLAN_FAIL, PLAN_ALIGNED = (1 << i for i in range(8))
+# include/qdec.h QD_BP_* / QD_FIN_* -> the kernel family last_kernels() names
+# ("": the workgroup kernels record no name)
+PLAN_BP = {0: "qdec::bp_wave_kernel", 1: "qdec::bp_ms_wave_kernel", 2: "qdec::bp_ms_cmp_kernel",
+           3: "qdec::bp_group_kernel", 4: {"f32": "qdec::bp_ms_lds_kernel", "f64": "qdec::bp_ms_lds64_kernel"}, 5: ""}
+PLAN_FIN = {0: "", 1: "", 2: "qdec::ssf_lut_kernel", 3: "qdec::ssf_wave_kernel", 4: "qdec::ssf_wave_kernel",
+            5: "qdec::ssf_wave_kernel", 6: "", 7: "", 8: ""}
+
+
+def _plan(lib, h, row, B=128):
+    """qd_graph_plan for a tools/record_dispatch.py row on host graph h."""
+    import ctypes as C
+
+    from exp_ldpc_amd import _abi
+    from exp_ldpc_amd.decoder import OPTIONS, SSF_KERNELS, parse_bp_method, parse_precision
+    for name in OPTIONS:  # back to the defaults, then the row's choices
+        default = {"compact": 1, "triage_it1": 1, "ssf": 0, "lds_kernel": -1, "group_kernel": -1, "ssf_inc": 1,
+                   "block_wg": 0, "group_mb": 0, "ssf_fuse": 0}[name]
+        value = row["options"].get(name, default)
+        _abi.check(lib.qd_graph_set_option(h, OPTIONS[name], SSF_KERNELS.get(value, value)), name)
+    _abi.check(lib.qd_graph_set_wave_occupancy(h, row["occ"]), "occupancy")
+    prm = _abi.QdParams(20, parse_bp_method(row["method"]), parse_precision(row["precision"]), int(row["ssf"]), 0,
+                        _abi.QD_INPUT_PACKED if row["packed"] else 0, 0.0)
+    present = PLAN_SYN | PLAN_READOUT | PLAN_FAIL | (PLAN_X if row["out"] == "x" else 0) | \
+        (0 if row["misaligned"] else PLAN_ALIGNED)
+    out = np.zeros(8, np.int32)
+    _abi.check(lib.qd_graph_plan(h, C.byref(prm), B, present, _abi.ptr(out)), "qd_graph_plan")
+    return dict(zip(("bp", "fin", "two_pass", "expand_packed", "fuse", "q_rpar", "placement", "buffers"),
+                    (int(v) for v in out)))
+
+
+def _check_plan_against_names(row, plan, names):
+    bp, ssf, pre = names
+    want_bp = PLAN_BP[plan["bp"]]
+    if isinstance(want_bp, dict):
+        want_bp = want_bp[row["precision"]]
+    assert bp.split("<")[0] == want_bp, (row["id"], plan, names)
+    assert ssf.split("<")[0] == PLAN_FIN[plan["fin"]], (row["id"], plan, names)
+    assert bool(pre) == bool(plan["two_pass"]) == (plan["bp"] == 2), (row["id"], plan, names)
+    # packed rows are expanded unless the triage reads them (its PK = true instantiation)
+    assert bool(plan["expand_packed"]) == (row["packed"] and not pre.endswith("true>")), (row["id"], plan, names)
+    if plan["two_pass"]:  # the compact kernel's last template argument is FUSE
+        assert bp.endswith(f", {plan['fuse']}>"), (row["id"], plan, names)
+        assert plan["q_rpar"] == int(row["ssf"]) and plan["buffers"] & 2
+    assert (plan["fin"] == 0) == (not row["ssf"] and plan["bp"] != 4), (row["id"], plan)
+    assert bool(plan["buffers"] & 1) == (plan["fin"] != 0) and bool(plan["buffers"] & 4) == bool(plan["expand_packed"])
+    if "ssf" in row["options"] and row["ssf"] and plan["fin"] != 1:
+        assert plan["fin"] == {"scan": 3, "scan_gather": 4, "scan_nosplit": 5}[row["options"]["ssf"]]
+
+
+def _check_plans_of(graphs):
+    from exp_ldpc_amd import _abi
+    from tools import record_dispatch as rd
+    lib = _abi.load()
+    golden = rd.load_golden()
+    assert set(golden) == {r["id"] for r in rd.ROWS}
+    for name in graphs:
+        hz, hx, lz = rd.load_graph(name)
+        h, _, _ = _host_graph(lib, hz, gens=hx, lz=lz, probs=0.02)
+        try:
+            rows = rd.rows_of([name])
+            assert rows
+            for row in rows:
+                _check_plan_against_names(row, _plan(lib, h, row), golden[row["id"]])
+        finally:
+            lib.qd_graph_destroy(h)
+
+
+def test_plan_matches_recorded_dispatch():
+    """The pure planner (qd_graph_plan on host-only graphs, no GPU) against what
+    the launch layer actually launched before the plan existed
+    (tests/golden/dispatch_names.json, recorded on an MI355X by
+    tools/record_dispatch.py): BP and SSF kernel families, pre-pass or not, and
+    which packed decodes the triage reads directly; the wave graph and the two
+    workgroup graphs."""
+    from tools import record_dispatch as rd
+    _check_plans_of([rd.WAVE_GRAPH] + rd.BLOCK_GRAPHS)
+
+
+@pytest.mark.slow
+def test_plan_matches_recorded_dispatch_c4():
+    """The same on the n = 10^4 graph (LDS-resident, slot-group and HBM-slice
+    workgroup kernels).  Marked slow: 8 s, nearly all of it computing the code's
+    logicals (gf2.css_logicals) and building the host tables; the 14 plans
+    themselves take milliseconds."""
+    from tools import record_dispatch as rd
+    _check_plans_of([rd.LARGE_GRAPH])
+
+
+def test_plan_expands_packed_rows_the_triage_cannot_step():
+    """A wave shape may have more check rounds than a packed syndrome row has
+    words (m <= 64 on (2, 3, *); m <= 128 on (4, 9, 8)): the triage steps RC
+    words per shot, so those two-pass decodes expand their rows first; where RC
+    = ceil(m / 64) the triage reads the words."""
+    import ctypes as C
+
+    from exp_ldpc_amd import _abi
+    from test_gpu_compact import _random_graph
+    lib = _abi.load()
+    for (m, n), direct in (((48, 160), False), ((100, 400), False), ((110, 170), True), ((120, 230), True)):
+        rng = np.random.default_rng(m * 1000 + n)
+        H = _random_graph(rng, m, n)
+        lz = (rng.random((3, n)) < 0.1).astype(np.uint8)
+        h, _, _ = _host_graph(lib, H, lz=lz, probs=0.02)
+        try:
+            for precision in (_abi.QD_F64, _abi.QD_F32):
+                prm = _abi.QdParams(20, _abi.QD_MIN_SUM, precision, 0, 0, _abi.QD_INPUT_PACKED, 0.0)
+                out = np.zeros(8, np.int32)
+                _abi.check(lib.qd_graph_plan(h, C.byref(prm), 65, PLAN_SYN | PLAN_READOUT | PLAN_FAIL | PLAN_ALIGNED,
+                                             _abi.ptr(out)), "qd_graph_plan")
+                assert out[0] == 2 and out[2] == 1, (m, n, out)  # the two-pass path either way
+                assert bool(out[3]) == (not direct), (m, n, out)
+        finally:
+            lib.qd_graph_destroy(h)
+
+
 def test_kernel_options_are_handle_state_not_environment(code225):
     """Kernel choices are per-handle options (qd_graph_set_option): defaults,
     round trip, range checks, unknown options refused; and no source file of

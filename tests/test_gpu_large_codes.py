@@ -507,3 +507,16 @@ def test_c5_run_simulation_bpssf_matches_oracle(gpu_available, oracle_lib, c5):
     ref = oracle_lib.decode(hz, pr, syn, method="ms", precision="f64", max_iter=50, ssf=True, gens=hx, lz=lz,
                             readout=rd, want_llr=False, ssf_impl="fast")
     assert np.array_equal(fails, ref["fail"].astype(bool))
+
+
+def test_hgp10k_dispatch_matches_recorded_names(gpu_available, hgp10k):
+    """C4 rows of tools/record_dispatch.py's table (LDS-resident f32 / f64, the
+    slot-group kernel forced, the workgroup kernel with HBM slices; SSF on and
+    off) launch the kernels recorded in tests/golden/dispatch_names.json."""
+    from tools import record_dispatch as rd
+    hx, hz, lz = hgp10k
+    golden = rd.load_golden()
+    rows = rd.rows_of([rd.LARGE_GRAPH])
+    assert len(rows) == 14
+    for row in rows:
+        assert rd.run_row(row, (hz, hx, lz)) == golden[row["id"]], row["id"]

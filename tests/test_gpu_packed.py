@@ -156,3 +156,75 @@ def test_packed_inputs_on_expanding_paths(gpu_available, oracle_lib):
     b = dec4.decode(pack_rows(s4), want=("x", "iters", "status", "ssf_steps"), packed=True)
     for k in a:
         assert np.array_equal(a[k], b[k]), ("c4", k)
+
+
+# Wave shapes with more check rounds than a packed syndrome row has words:
+# (48, 160) lands on (2, 3, *) with ceil(m / 64) = 1, (100, 400) on (4, 9, 8)
+# with ceil(m / 64) = 2
+WIDE_SHAPES = {(48, 160): (2, 3), (100, 400): (4, 9)}
+_WIDE = {}
+
+
+def _wide_case(oracle_lib, mn, precision):
+    """Graph, priors, logicals, 700 shots and the oracle's decode of them (once
+    per case; smaller batches are prefixes, shots being independent)."""
+    if (mn, precision) not in _WIDE:
+        from test_gpu_compact import _random_graph
+        m, n = mn
+        rng = np.random.default_rng(m * 1000 + n)
+        H = _random_graph(rng, m, n)
+        probs = rng.uniform(0.005, 0.05, n)
+        L = (rng.random((3, n)) < 0.05).astype(np.uint8)
+        e = (rng.random((700, n)) < 0.02).astype(np.uint8)
+        e[5:200:3] = 0
+        syn = np.ascontiguousarray(((H @ e.T).T % 2).astype(np.uint8))
+        rd = np.ascontiguousarray((e ^ (rng.random((700, n)) < 0.01)).astype(np.uint8))
+        ref = oracle_lib.decode(H, probs, syn, method="ms", precision=precision, max_iter=20, lz=L, readout=rd,
+                                want_llr=False)
+        _WIDE[(mn, precision)] = (H, probs, L, syn, rd, ref)
+    return _WIDE[(mn, precision)]
+
+
+@pytest.mark.parametrize("mn", sorted(WIDE_SHAPES))
+def test_oracle_decodes_the_wide_shape_graphs(oracle_lib, mn):
+    """The generic CPU oracle handles both graphs (converged and unconverged
+    shots, failures and successes), so it can referee the GPU test below."""
+    for precision in ("f64", "f32"):
+        H, _, _, syn, _, ref = _wide_case(oracle_lib, mn, precision)
+        assert H.shape == mn and ref["iters"].shape == (700,)
+        conv = (ref["status"] & 1).astype(bool)
+        assert 0 < conv.sum() and ref["iters"][conv].max() <= 20 and 0 < ref["fail"].sum() < 700
+        zero = syn.sum(1) == 0  # positive priors: x = 0 satisfies them at the first check (ldpc counts it as 1)
+        assert zero.sum() > 50 and np.all(conv[zero]) and np.all(ref["iters"][zero] == 1)
+
+
+@pytest.mark.parametrize("B", [1, 65, 700])
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+@pytest.mark.parametrize("mn", sorted(WIDE_SHAPES))
+def test_packed_rows_shorter_than_the_check_rounds(gpu_available, oracle_lib, mn, precision, B):
+    """The packed triage steps through m_pad / 64 words per syndrome row; where
+    a row holds fewer (ceil(m / 64)) the plan expands the rows and runs the
+    byte-row triage: same bytes as the byte-row decode, which equals the oracle."""
+    import torch
+    from exp_ldpc_amd.decoder import Decoder, pack_rows
+    H, probs, L, syn, rd, ref = _wide_case(oracle_lib, mn, precision)
+    rc, rv = WIDE_SHAPES[mn]
+    assert rc > -(-mn[0] // 64)
+    dec = Decoder(H, probs, method="ms", precision=precision, max_iter=20, logicals=L)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+    res = []
+    for packed in (False, True):
+        o = {k: torch.full((B,), 77, dtype=dt, device="cuda") for k, dt in
+             (("iters", torch.int32), ("status", torch.uint8), ("fail", torch.uint8))}
+        if packed:
+            dec.decode_device(B, syn=t(pack_rows(syn[:B]).view(np.int64)), readout=t(pack_rows(rd[:B]).view(np.int64)),
+                              packed=True, **o)
+        else:
+            dec.decode_device(B, syn=t(syn[:B]), readout=t(rd[:B]), **o)
+        torch.cuda.synchronize()
+        bp_k, _, pre_k = dec.last_kernels()
+        assert "bp_ms_cmp_kernel" in bp_k and pre_k == f"qdec::ms_triage_kernel<{rc}, {rv}, false>", (bp_k, pre_k)
+        res.append({k: v.cpu().numpy() for k, v in o.items()})
+    for k in res[0]:
+        assert np.array_equal(res[0][k], ref[k][:B]), (k, "bytes vs oracle")
+        assert np.array_equal(res[1][k], res[0][k]), (k, "packed vs bytes")

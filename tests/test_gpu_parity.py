@@ -660,3 +660,26 @@ def test_lean_zero_messages(gpu_available, oracle_lib, precision, lean_path):
                                 lz=lz, readout=rd, want_llr=False, ssf_impl="fast")
         for k in out:
             assert np.array_equal(out[k].cpu().numpy(), ref[k]), (ci, k)
+
+
+# ---------------------------------------------------------------- dispatch
+def _dispatch_rows():
+    from tools import record_dispatch as rd
+    return rd.rows_of([rd.WAVE_GRAPH] + rd.BLOCK_GRAPHS)
+
+
+@pytest.fixture(scope="module")
+def dispatch_graphs():
+    from tools import record_dispatch as rd
+    return {name: rd.load_graph(name) for name in [rd.WAVE_GRAPH] + rd.BLOCK_GRAPHS}, rd.load_golden()
+
+
+@pytest.mark.parametrize("row", _dispatch_rows(), ids=lambda r: r["id"])
+def test_dispatch_matches_recorded_names(gpu_available, dispatch_graphs, row):
+    """Every configuration of tools/record_dispatch.py's table on the wave graph
+    and two workgroup graphs launches exactly the kernels recorded in
+    tests/golden/dispatch_names.json (BP, SSF and pre-pass instantiations,
+    template arguments included)."""
+    from tools import record_dispatch as rd
+    graphs, golden = dispatch_graphs
+    assert rd.run_row(row, graphs[row["graph"]]) == golden[row["id"]]
