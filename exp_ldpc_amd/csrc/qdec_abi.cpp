@@ -70,7 +70,8 @@ struct qd_graph : HostGraph {
     int device = 0;
     int num_cus = 0;
     hipStream_t stream = nullptr;
-    bool has_priors = false;
+    bool has_priors = false;   // BP priors: every probability inside (0, 1)
+    bool has_thr = false;      // qd_graph_set_priors succeeded: the fault sampler's thresholds exist
     // workspace for the host-buffer API (grow only)
     void* ws = nullptr;
     size_t ws_bytes = 0;
@@ -332,6 +333,8 @@ void check_params(const qd_graph* g, const qd_params* p) {
     if (!p) throw Fail(-2, "null params");
     if (p->method != QD_MIN_SUM && p->method != QD_PRODUCT_SUM) throw Fail(-3, "unknown BP method");
     if (p->precision != QD_F32 && p->precision != QD_F64) throw Fail(-4, "unknown precision");
+    if (!g->has_priors && g->has_thr)
+        throw Fail(-51, "the graph's priors hold a 0 or a 1: it samples faults, BP needs probabilities inside (0, 1)");
     if (!g->has_priors) throw Fail(-5, "priors not set (qd_graph_set_priors)");
     if (p->ssf && g->dg.n_gen <= 0) throw Fail(-6, "SSF requested but the graph has no flip sets");
 }
@@ -670,8 +673,9 @@ int qd_graph_set_priors(qd_graph* G, const double* probs) {
     return guarded([&] {
         check_graph(G);
         set_device(G);
-        set_priors(G, probs);
-        G->has_priors = true;
+        set_priors(G, probs);  // on a throw the previous tables and flags stand
+        G->has_priors = G->bp_priors;
+        G->has_thr = true;
     });
 }
 
@@ -763,14 +767,10 @@ static int sample_storage(qd_graph* G, int32_t rounds, double p_data, double p_m
         if (!syn || !readout) throw Fail(-60, "invalid sampler arguments");
         if (packed && (((uintptr_t)syn | (uintptr_t)readout) & 7)) throw Fail(-60, "packed rows must be 8-B aligned");
         if (G->dg.fold_blocks != 1 || G->dg.n_data != G->dg.n) throw Fail(-61, "sampler needs a plain code graph (H = Hz)");
-        auto thr = [](double p) -> uint32_t {
-            if (!(p > 0)) return 0u;
-            const double v = std::floor(p * 4294967296.0);
-            return v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v;
-        };
         set_device(G);
-        const int rc = launch_sample_storage(G->dg, rounds, thr(2.0 * p_data / 3.0), thr(p_meas), seed, stream_id,
-                                             shot0, B, syn, readout, G->num_cus, (hipStream_t)stream, packed);
+        const int rc = launch_sample_storage(G->dg, rounds, bern_threshold(2.0 * p_data / 3.0), bern_threshold(p_meas),
+                                             seed, stream_id, shot0, B, syn, readout, G->num_cus, (hipStream_t)stream,
+                                             packed);
         if (rc != 0) throw Fail(-102, std::string("sampler launch failed: ") + hipGetErrorString((hipError_t)rc));
     });
 }
@@ -786,6 +786,36 @@ int qd_sample_storage_packed_device(qd_graph* G, int32_t rounds, double p_data, 
                                     void* stream) {
     return sample_storage(G, rounds, p_data, p_meas, seed, stream_id, shot0, B, reinterpret_cast<uint8_t*>(syn),
                           reinterpret_cast<uint8_t*>(readout), stream, true);
+}
+
+int qd_sample_faults_device(qd_graph* G, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B, int32_t flags,
+                            void* det, void* faults, uint8_t* obs, void* stream) {
+    return guarded([&] {
+        check_graph(G);
+        if (G->host_only) throw Fail(-16, "host-only graph (qd_graph_create_host): no device to sample on");
+        if (B < 0 || (flags & ~QD_INPUT_PACKED)) throw Fail(-60, "invalid sampler arguments");
+        const DevGraph& g = G->dg;
+        if (!G->has_thr || !G->smp_thr) throw Fail(-63, "priors not set (qd_graph_set_priors): no fault probabilities");
+        if (g.fold_blocks != 1 || g.n_data != g.n)
+            throw Fail(-64, "fault sampler needs an unfolded graph (fold_blocks = 1, n_data = n)");
+        if (B == 0) return;
+        if (!det) throw Fail(-66, "null detector buffer");
+        if (obs && g.k <= 0) throw Fail(-65, "observables requested but the graph has no logicals");
+        const bool packed = (flags & QD_INPUT_PACKED) != 0;
+        if (packed && (((uintptr_t)det | (uintptr_t)faults) & 7)) throw Fail(-67, "packed rows must be 8-B aligned");
+        set_device(G);
+        const int rc = launch_sample_faults(g, G->smp_thr, G->smp_crow, seed, stream_id, shot0, B, packed, det, faults,
+                                            obs, G->num_cus, (hipStream_t)stream);
+        if (rc != 0) throw Fail(-102, std::string("sampler launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int qd_graph_sample_tables_copy(const qd_graph* G, uint32_t* thr, int32_t* crow) {
+    return guarded([&] {
+        check_graph(G);
+        if (!G->host_only) throw Fail(-16, "table copies are kept for host-only graphs (qd_graph_create_host)");
+        sample_tables_copy(G, thr, crow);
+    });
 }
 
 int qd_osd_device_supported(const qd_graph* G) {

@@ -216,6 +216,12 @@ size_t block_scratch_floor(const DevGraph& g, const DecodePlan& p, int num_cus, 
 int launch_sample_storage(const DevGraph& g, int rounds, uint32_t thr_data, uint32_t thr_meas,
                           uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
                           uint8_t* syn, uint8_t* readout, int num_cus, hipStream_t stream, bool packed = false);
+// B shots of the graph's own faults (sample_faults_kernel): det = H e, faults = e
+// (nullable), obs = F e (nullable; F = the graph's logicals); byte rows, or u64
+// words when packed.  thr / crow: HostGraph::smp_thr / smp_crow (qdec_tables.h)
+int launch_sample_faults(const DevGraph& g, const uint32_t* thr, const int32_t* crow, uint32_t seed,
+                         uint32_t stream_id, int64_t shot0, int64_t B, bool packed, void* det, void* faults,
+                         uint8_t* obs, int num_cus, hipStream_t stream);
 int launch_count_flags(const uint8_t* flags, int64_t B, uint8_t mask, int64_t* out, hipStream_t stream);
 
 // ---------------------------------------------------------------- HGP kernel

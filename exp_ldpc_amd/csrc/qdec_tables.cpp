@@ -669,6 +669,8 @@ void build_tables(HostGraph* G, int m, int n) {
     g.edge_csc = G->arena->upload(edge_csc);
     g.row_ptr = G->arena->upload(G->row_ptr);
     g.col_idx = G->arena->upload(ci_pad);
+    G->smp_crow = G->arena->upload(G->col_rows);  // fault sampler: the column walk
+    G->smp_thr = nullptr;
     int rc = 0, rv = 0, drc = 0;
     g.wave = (g.max_rdeg <= kDR && g.max_cdeg <= kDC && pick_wave_shape(m, n, g.max_rdeg, &rc, &rv, &drc)) ? 1 : 0;
     if (!g.wave) {  // workgroup kernels: plain 64-padding, no wave tables
@@ -1089,11 +1091,32 @@ void set_priors(HostGraph* G, const double* probs) {
     DevGraph& g = G->dg;
     std::vector<double> ms64(g.n_pad, 0.0), ps64(g.n_pad, 0.0);
     std::vector<float> ms32(g.n_pad, 0.0f), ps32(g.n_pad, 0.0f);
+    std::vector<uint32_t> thr(((size_t)g.n + 3) / 4 * 4, 0u);  // fault sampler; pads never fire
+    bool open = true;
     for (int j = 0; j < g.n; ++j) {
         const double p = probs[j];
+        if (!(p >= 0.0 && p <= 1.0)) throw Fail(-51, "channel probability outside [0, 1]");
         // open interval: keeps every BP message finite (and NaN-free), the
         // precondition of the kernels' min/med3 check-node formulation
-        if (!(p > 0.0 && p < 1.0)) throw Fail(-51, "channel probability outside (0, 1)");
+        open = open && p > 0.0 && p < 1.0;
+        thr[j] = bern_threshold(p);
+    }
+    if (!open) {  // a certain or impossible fault: a graph to sample from, not to decode on
+        G->prior_arena->release();
+        for (auto& m2 : g.prior)
+            for (auto& q : m2) q = nullptr;
+        for (auto& m2 : g.eprior)
+            for (auto& q : m2) q = nullptr;
+        g.ms_prior[QD_F64] = g.ms_prior[QD_F32] = nullptr;
+        g.it1_vchk = g.it1_cvar = nullptr;
+        g.it1_lut[QD_F64] = g.it1_lut[QD_F32] = nullptr;
+        g.ms_allpos = 0;
+        G->smp_thr = G->prior_arena->upload(thr);
+        G->bp_priors = false;
+        return;
+    }
+    for (int j = 0; j < g.n; ++j) {
+        const double p = probs[j];
         ms64[j] = std::log((1 - p) / p);   // ldpc v1: log((1-p)/p)
         ps64[j] = p / (1 - p);             // ldpc v1: p/(1-p)
         ms32[j] = (float)ms64[j];
@@ -1138,6 +1161,8 @@ void set_priors(HostGraph* G, const double* probs) {
         g.eprior[QD_PRODUCT_SUM][QD_F64] = G->prior_arena->upload(eps64);
         g.eprior[QD_PRODUCT_SUM][QD_F32] = G->prior_arena->upload(eps32);
     }
+    G->smp_thr = G->prior_arena->upload(thr);
+    G->bp_priors = true;
 }
 
 void table_digest(const HostGraph* G, uint64_t* digest, int64_t* bytes) {
@@ -1150,6 +1175,13 @@ void table_digest(const HostGraph* G, uint64_t* digest, int64_t* bytes) {
         }
     if (digest) *digest = h;
     if (bytes) *bytes = total;
+}
+
+void sample_tables_copy(const HostGraph* G, uint32_t* thr, int32_t* crow) {
+    const DevGraph& g = G->dg;
+    if (!G->smp_thr) throw Fail(-63, "priors not set (qd_graph_set_priors): no fault thresholds");
+    if (thr) std::memcpy(thr, G->smp_thr, (size_t)g.n * 4);
+    if (crow && g.E > 0) std::memcpy(crow, G->smp_crow, (size_t)g.E * 4);
 }
 
 void ssf_tables_copy(const DevGraph& g, uint32_t* lut, uint32_t* off, uint32_t* lcw, uint32_t* tog, int32_t* g_pad,

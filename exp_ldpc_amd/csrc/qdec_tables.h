@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -23,6 +24,16 @@ struct Fail : std::runtime_error {
     int code;
     Fail(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
+
+// Bernoulli(p) as a 32-bit threshold: a uniform u32 word u fires when u < thr.
+// floor(p 2^32) clamped to 0xFFFFFFFF; anything not > 0 (NaN included) never
+// fires.  The one conversion of both samplers (qd_sample_storage_*: its two
+// event probabilities; qd_sample_faults_device: smp_thr).
+inline uint32_t bern_threshold(double p) {
+    if (!(p > 0)) return 0u;
+    const double v = std::floor(p * 4294967296.0);
+    return v >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)v;
+}
 
 // Where the builders put a finished table: a copy that stays valid until
 // release().  At least 16 bytes are allocated, so an empty table still has an
@@ -59,6 +70,17 @@ struct HostGraph {
     std::vector<int> ms_var_of_slot;
     std::unique_ptr<TableSink> arena;        // graph tables
     std::unique_ptr<TableSink> flip_arena, lz_arena, prior_arena;
+    // set_priors: every probability lay inside (0, 1), so the BP priors exist;
+    // false after a call with a 0 or a 1 among them (sampler thresholds only)
+    bool bp_priors = false;
+    // fault sampler (sample_faults_kernel, qdec_sample.hip; kept beside DevGraph,
+    // which every decode kernel takes by value): column j fires when a Philox
+    // word is < smp_thr[j] (bern_threshold of the probability last given to
+    // set_priors; zero entries pad n to a multiple of 4; nullptr before the
+    // first set_priors), and then toggles the rows smp_crow[col_ptr[j] ..
+    // col_ptr[j + 1]) (the row of each edge in CSC order)
+    const uint32_t* smp_thr = nullptr;   // [(n + 3) / 4 * 4], prior_arena
+    const int32_t* smp_crow = nullptr;   // [max(E, 1)], arena
 };
 
 // The build sequence of a graph handle.  init_graph expects a validated CSR
@@ -70,11 +92,16 @@ void init_graph(HostGraph* G, int m, int n, const int32_t* row_ptr, const int32_
 void set_flipsets(HostGraph* G, int32_t n_gen, const int32_t* gen_ptr, const int32_t* gen_idx);
 void set_logicals(HostGraph* G, int32_t k, const uint8_t* lz);  // dense [k][n_data]
 void set_logicals_csr(HostGraph* G, int32_t k, const int32_t* lz_ptr, const int32_t* lz_idx);
+// probabilities in [0, 1].  Inside (0, 1) throughout: the BP priors and the
+// sampler thresholds; with a 0 or a 1 among them BP has no finite message, so
+// only the thresholds are built (G->bp_priors = false; decodes then refuse)
 void set_priors(HostGraph* G, const double* probs);
 
 // FNV-1a over every table in upload order (graph, flip sets, logicals, priors)
 // and their total size; the graph's sinks must be HostSinks
 void table_digest(const HostGraph* G, uint64_t* digest, int64_t* bytes);
+// the fault sampler's tables of a host-only graph: thr[n], crow[E] (null outputs are skipped)
+void sample_tables_copy(const HostGraph* G, uint32_t* thr, int32_t* crow);
 // the table-driven wave SSF tables of a host-only graph (null outputs are skipped)
 void ssf_tables_copy(const DevGraph& g, uint32_t* lut, uint32_t* off, uint32_t* lcw, uint32_t* tog, int32_t* g_pad,
                      int32_t* m_pad);

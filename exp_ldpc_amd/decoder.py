@@ -264,6 +264,27 @@ class Decoder:
             int(stream_id) & 0xFFFFFFFF, int(shot0), int(B), _abi.ptr(syn), _abi.ptr(readout), C.c_void_p(stream)),
             "qd_sample_storage_device")
 
+    def sample_faults_device(self, seed: int, stream_id: int, shot0: int, B: int, det, faults=None, obs=None,
+                             stream=None, packed: bool = False) -> None:
+        """Draw B shots of this graph's own faults (qd_sample_faults_device):
+        column j fires with the probability last given to set_priors.  Writes
+        det = H e (uint8 [B][m]), faults = e (uint8 [B][n], optional) and obs =
+        F e (uint8 [B][k], optional; F = the logicals).  packed=True writes det
+        and faults bit-packed: int64 [B][ceil(m/64)] / [B][ceil(n/64)]
+        (pack_rows of the byte rows)."""
+        if stream is None:
+            stream = _current_stream(self.device)
+        B = int(B)
+        row_t = "int64" if packed else "uint8"
+        wcols = (lambda c: (c + 63) // 64) if packed else (lambda c: c)
+        self._check_device_buffer("det", det, row_t, B * wcols(self.m))
+        self._check_device_buffer("faults", faults, row_t, B * wcols(self.n))
+        self._check_device_buffer("obs", obs, "uint8", B * self.k)
+        _abi.check(self._lib.qd_sample_faults_device(
+            self._handle, int(seed) & 0xFFFFFFFF, int(stream_id) & 0xFFFFFFFF, int(shot0), B,
+            QD_INPUT_PACKED if packed else 0, _abi.ptr(det), _abi.ptr(faults), _abi.ptr(obs), C.c_void_p(stream)),
+            "qd_sample_faults_device")
+
     # ------------------------------------------------------------ OSD on the device
     @property
     def osd_device_supported(self) -> bool:

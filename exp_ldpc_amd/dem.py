@@ -28,7 +28,9 @@ This module supplies the two pieces without Stim:
 
 ``sample_dem`` draws detector samples by sampling every fault independently
 from its prior -- for independent fault mechanisms the distribution Stim's
-detector sampler produces.
+detector sampler produces.  ``sample_dem_device`` does the same on the GPU
+(``qd_sample_faults_device``, counter-based Philox), for the batched pipeline
+``experiment.DemPipeline``.
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ import numpy as np
 import scipy.sparse as sp
 
 __all__ = ["DemInstruction", "DetectorErrorModel", "parse_dem", "DetectorSpacetimeCode", "storage_experiment_dem",
-           "sample_dem"]
+           "sample_dem", "sample_dem_device"]
 
 
 @dataclass
@@ -240,3 +242,30 @@ def sample_dem(code: DetectorSpacetimeCode, shots: int, seed: int = 0) -> Tuple[
     det = (code.fault_check_matrix.astype(np.int64) @ f.T).T % 2
     obs = (code.fault_map.astype(np.int64) @ f.T).T % 2
     return np.asarray(det, dtype=np.uint8), np.asarray(obs, dtype=np.uint8)
+
+
+def sample_dem_device(decoder, shots: int, seed: int = 0, stream_id: int = 0, shot0: int = 0, packed: bool = False,
+                      want_obs: bool = True):
+    """The device counterpart of ``sample_dem``: ``decoder`` is a ``Decoder`` on a
+    DEM's fault check matrix with the fault priors (and the fault map as
+    logicals when observables are wanted).  Returns device tensors
+    ``(det, faults, obs)``: detectors ``H e`` and the fault vectors ``e``
+    themselves (uint8 rows, or with ``packed`` int64 words in the
+    QD_INPUT_PACKED layout) and observables ``F e`` (uint8 [B, K]; None without
+    ``want_obs`` or without logicals).  Counter-based (Philox keyed by seed and
+    stream_id, counted by fault word and shot0 + row): the shots do not depend
+    on how they are split across calls or devices, and differ from
+    ``sample_dem``'s numpy stream."""
+    import torch
+    B = int(shots)
+    dev = torch.device("cuda", decoder.device)
+    if packed:
+        det = torch.empty((B, (decoder.m + 63) // 64), dtype=torch.int64, device=dev)
+        faults = torch.empty((B, (decoder.n + 63) // 64), dtype=torch.int64, device=dev)
+    else:
+        det = torch.empty((B, decoder.m), dtype=torch.uint8, device=dev)
+        faults = torch.empty((B, decoder.n), dtype=torch.uint8, device=dev)
+    obs = torch.empty((B, decoder.k), dtype=torch.uint8, device=dev) if want_obs and decoder.k else None
+    with torch.cuda.device(dev):
+        decoder.sample_faults_device(seed, stream_id, shot0, B, det, faults, obs, packed=packed)
+    return det, faults, obs

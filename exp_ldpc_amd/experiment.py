@@ -16,6 +16,10 @@ device.  Decoder modes (``--decoder_mode``):
                      (_experiment.py:128-151); the storage experiment's DEM is
                      written by dem.storage_experiment_dem (any R)
 
+A detector error model of the user's own (any noise model, Stim's DEM text) is
+sampled on the device from its fault probabilities and decoded in batches by
+``DemPipeline`` / ``run_dem_simulation`` (BP only, like ``BPDetectorCorrect``).
+
 OSD runs on the GPU for the shots BP did not converge on (Decoder.osd_device,
 csrc/qdec_osd.hip), fused with the fold and the failure check; graphs too large
 for that kernel use the host stage (osd.py).
@@ -44,7 +48,7 @@ from .osd import OsdSolver
 from .spacetime import SpacetimeCode, SpacetimeCodeSingleShot
 from .storage_sim import build_storage_simulation
 
-__all__ = ["DECODER_MODES", "BatchPipeline", "ShardError", "run_shards", "BPOSDCorrect", "BPOSDHybridCorrect", "BPOSDCorrectSingleShot",
+__all__ = ["DECODER_MODES", "BatchPipeline", "DemPipeline", "run_dem_simulation","ShardError", "run_shards", "BPOSDCorrect", "BPOSDHybridCorrect", "BPOSDCorrectSingleShot",
            "BPSSFCorrect", "BPDetectorCorrect", "run_simulation", "add_bposd_args", "unpack_bposd_args", "load_code", "p_sweep",
            "p_sweep_main", "parse_sweep_spec"]
 
@@ -64,6 +68,89 @@ class BatchResult:
     iters_sum: int
     ssf_steps_sum: int
     corrections: np.ndarray | None = None  # uint8[B, n] when requested
+    detail: dict | None = None  # DemPipeline.run(want_detail=True): per-shot host arrays
+
+
+class DemPipeline:
+    """Sample a detector error model on the device and decode it in batches: the
+    batched counterpart of ``BPDetectorCorrect`` (reference _experiment.py:128-151
+    with Stim's ``compile_detector_sampler().sample``, :193-194) for any DEM, given
+    as DEM text or a parsed model.  One ``Decoder`` on the fault check matrix H
+    with the fault priors and the fault map F as logicals.  The sampler writes the
+    fault vector e and H e; the decode takes e as its ``readout``, so its fused
+    check any(F (e ^ x)) = any(F e ^ F x) = any(obs ^ F x) is the reference's
+    failure flag (:143-151, :204).  BP only, like the reference's class."""
+
+    def __init__(self, detector_error_model, bp_osd_options: Dict, *, device: int = 0, precision: str = "f64"):
+        from .dem import DetectorSpacetimeCode
+        self.dem = DetectorSpacetimeCode(detector_error_model)
+        self.device = int(device)
+        o = bp_osd_options
+        fmap = self.dem.fault_map
+        self.k = fmap.shape[0]
+        # the fault map stays sparse: Decoder.set_logicals hands over CSR supports,
+        # so a DEM whose dense k x n map would take tens of MB never builds it
+        self.dec = Decoder(self.dem.fault_check_matrix, self.dem.fault_priors, method=o.get("bp_method", "ps"),
+                           precision=precision, max_iter=int(o.get("max_iter", 0) or 0),
+                           ms_scaling=float(o.get("ms_scaling_factor", 0.0)), logicals=fmap if self.k else None,
+                           device=self.device)
+
+    def decoders(self):
+        return [self.dec]
+
+    def run(self, B: int, seed: int, stream_id: int = 0, shot0: int = 0, packed: bool = True,
+            want_detail: bool = False) -> BatchResult:
+        """Shots shot0 .. shot0 + B of stream (seed, stream_id).  packed: the
+        sampler writes bit-packed rows and the decode reads them
+        (QD_INPUT_PACKED); the results do not depend on it.  want_detail: the
+        result's ``detail`` holds the shots' det, obs, iters and status."""
+        from .dem import sample_dem_device
+        from .decoder import unpack_rows
+        torch = _torch()
+        B = int(B)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            det, faults, obs = sample_dem_device(self.dec, B, seed, stream_id, shot0, packed=packed,
+                                                 want_obs=want_detail)
+            iters = torch.zeros(B, dtype=torch.int32, device=dev)
+            status = torch.zeros(B, dtype=torch.uint8, device=dev)
+            fail = torch.zeros(B, dtype=torch.uint8, device=dev)
+            if self.k:
+                self.dec.decode_device(B, syn=det, readout=faults, iters=iters, status=status, fail=fail,
+                                       packed=packed)
+            else:  # no observable: nothing can fail
+                self.dec.decode_device(B, syn=det, iters=iters, status=status, packed=packed)
+            detail = None
+            if want_detail:
+                det_h = det.cpu().numpy()
+                detail = {"det": unpack_rows(det_h.view(np.uint64), self.dec.m) if packed else det_h,
+                          "obs": obs.cpu().numpy() if obs is not None else np.zeros((B, 0), np.uint8),
+                          "iters": iters.cpu().numpy(), "status": status.cpu().numpy()}
+            return BatchResult(fail=fail.cpu().numpy().astype(bool), bp_converged=int((status & 1).sum().item()),
+                               iters_sum=int(iters.to(torch.int64).sum().item()), ssf_steps_sum=0, detail=detail)
+
+
+def run_dem_simulation(samples, detector_error_model, bp_osd_options, *, seed: int, stream_id: int = 0,
+                       shot0: int = 0, device: int = 0, batch: int = 1 << 18, precision: str = "f64",
+                       stats: dict | None = None):
+    """Sample and decode `samples` shots of a detector error model (DEM text or a
+    parsed model) on one GPU; returns a bool ndarray of logical-failure flags,
+    shaped like run_simulation's.  Replaces the reference's per-shot loop over
+    Stim's detector samples and BPDetectorCorrect (_experiment.py:186-209) for a
+    user-supplied DEM; the flags do not depend on `batch`."""
+    pipe = DemPipeline(detector_error_model, bp_osd_options, device=device, precision=precision)
+    out = np.zeros(samples, dtype=bool)
+    agg = {"bp_converged": 0, "iters_sum": 0, "ssf_steps_sum": 0}
+    for start in range(0, samples, batch):
+        b = min(batch, samples - start)
+        res = pipe.run(b, seed, stream_id, shot0 + start)
+        out[start:start + b] = res.fail
+        agg["bp_converged"] += res.bp_converged
+        agg["iters_sum"] += res.iters_sum
+    if stats is not None:
+        stats.update(agg)
+    pipe.dec.close()
+    return out
 
 
 class BatchPipeline:

@@ -106,7 +106,10 @@ int qd_graph_set_logicals_csr(qd_graph* g, int32_t k, const int32_t* lz_ptr, con
 /* Per-column error probabilities (ldpc `error_rate` broadcast / `channel_probs`;
  * reference call sites _experiment.py:23-27, 37-40, 74-77, 106-113).  Converted
  * on the host to the ldpc initial messages log((1-p)/p) (min-sum) and p/(1-p)
- * (product-sum) in both precisions. */
+ * (product-sum) in both precisions, and to the fault sampler's thresholds
+ * (qd_sample_faults_device).  Probabilities lie in [0, 1] (-51 otherwise); a 0
+ * or a 1 among them leaves a graph that samples but does not decode (BP has no
+ * finite message for it: decodes return -51). */
 int qd_graph_set_priors(qd_graph* g, const double* channel_probs);
 
 /* Batched replacement of B calls to .decode(syndrome) (_experiment.py:82, 117,
@@ -156,6 +159,31 @@ int qd_sample_storage_device(qd_graph* g, int32_t rounds, double p_data, double 
 int qd_sample_storage_packed_device(qd_graph* g, int32_t rounds, double p_data, double p_meas,
                                     uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
                                     uint64_t* syn, uint64_t* readout, void* stream);
+
+/* Draw B shots of the graph's own faults: column j fires with the probability last
+ * given to qd_graph_set_priors.  Replaces Stim's compile_detector_sampler().sample
+ * (_experiment.py:193-194) for a DEM whose fault check matrix is this graph.
+ *   det    [B][m] u8, or with QD_INPUT_PACKED in flags u64 [B][ceil(m/64)]: H e
+ *   faults [B][n] u8 / u64 [B][ceil(n/64)]: e itself (nullable) -- pass it as the
+ *          decode's `readout`: with the fault map as logicals, fail = any(obs ^ F x)
+ *   obs    [B][k] u8: F e (nullable; needs logicals)
+ * Fault j fires when u < thr[j]: u = lane j % 4 of the Philox4x32-10 block with
+ * key (seed, stream_id) and counter (j / 4, 0, shot), shot = shot0 + row (64
+ * bits); thr[j] = floor(p_j 2^32) clamped to 2^32 - 1 (0 for p_j = 0), the
+ * storage sampler's conversion.  Results do not depend on how shots are split
+ * across calls, streams or devices.  Padding bits of packed rows are written 0.
+ * For sampling, qd_graph_set_priors takes probabilities in [0, 1]; a graph whose
+ * priors hold a 0 or a 1 can be sampled but not decoded (-51).  B = 0 returns 0
+ * and writes nothing.  Errors: -16 host-only graph, -60 B < 0 or unknown flags,
+ * -63 priors never set, -64 folded graph (fold_blocks != 1 or n_data != n),
+ * -65 obs without logicals, -66 det null, -67 packed buffer not 8-B aligned. */
+int qd_sample_faults_device(qd_graph* g, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
+                            int32_t flags, void* det, void* faults, uint8_t* obs, void* stream);
+/* Host-only graphs, for tests: the sampler's tables, thr[n] (above) and crow[nnz]
+ * (the row of each edge in column-major order: column j's rows, ascending, at
+ * crow[colptr[j] .. colptr[j+1])).  Either may be NULL.  -63 before the first
+ * qd_graph_set_priors. */
+int qd_graph_sample_tables_copy(const qd_graph* g, uint32_t* thr, int32_t* crow);
 
 /* Ordered-statistics decoding of shots BP did not converge on (the OSD stage of
  * ldpc v1 bposd_decoder; reference _experiment.py:23-27, 37-40, 77, 96-100).  Host

@@ -1,3 +1,6 @@
-"""qldpc.misc compatibility module (reference python/qldpc/misc/__init__.py)."""
+"""qldpc.misc compatibility module (reference python/qldpc/misc/__init__.py).
+DemPipeline and run_dem_simulation have no reference name: they are the batched
+road for a user-supplied detector error model."""
 from exp_ldpc_amd.experiment import (BPDetectorCorrect, BPOSDCorrect, BPOSDCorrectSingleShot,  # noqa: F401
-                                     BPOSDHybridCorrect, p_sweep, p_sweep_main, run_simulation)
+                                     BPOSDHybridCorrect, DemPipeline, p_sweep, p_sweep_main, run_dem_simulation,
+                                     run_simulation)
