@@ -1085,6 +1085,20 @@ int qd_graph_it1_tables_copy(const qd_graph* G, int32_t precision, uint16_t* lut
     });
 }
 
+int qd_graph_ms_state0_copy(const qd_graph* G, int32_t precision, void* state, uint16_t* sslot, int32_t* m_pad) {
+    return guarded([&] {
+        check_graph(G);
+        if (!G->host_only) throw Fail(-16, "table copies are kept for host-only graphs (qd_graph_create_host)");
+        if (precision != QD_F64 && precision != QD_F32) throw Fail(-4, "invalid precision");
+        const DevGraph& g = G->dg;
+        if (m_pad) *m_pad = g.m_pad;
+        if (!g.ms_state0[precision] || !g.ms_sslot[precision])
+            throw Fail(-39, "no first check state (not a wave-kernel graph, or priors not set)");
+        if (state) std::memcpy(state, g.ms_state0[precision], 2 * (size_t)g.m_pad * (precision == QD_F64 ? 8 : 4));
+        if (sslot) std::memcpy(sslot, g.ms_sslot[precision], (size_t)g.m_pad * 2);
+    });
+}
+
 int qd_graph_lds64_slots_copy(const qd_graph* G, uint16_t* etab, uint16_t* check_of_slot) {
     return guarded([&] {
         check_graph(G);

@@ -1040,8 +1040,10 @@ static int launch_bp_wave(const DevGraph& g, const DecodePlan& p, const DecodeAr
         // decodes may ask for more (qd_graph_set_wave_occupancy)
         const int cap = g.wave_occ > 0 ? g.wave_occ : (sizeof(T) == 8 ? 8 : 0);
         if (p.two_pass) {  // triage, then the listed shots
+            // the compact kernel starts every listed shot from the first check state
+            if (!g.ms_state0[sizeof(T) == 4 ? 1 : 0]) return (int)hipErrorInvalidValue;
             DecodeArgs b = a;
-            b.cmp_zero_ok = (g.ms_allpos >> (sizeof(T) == 4 ? 1 : 0)) & 1;
+            b.cmp_zero_ok =(g.ms_allpos >> (sizeof(T) == 4 ? 1 : 0)) & 1;
             // iteration 1 in the triage: the tables assume alpha_1 = 0.5 (the
             // default schedule); QD_OPT_TRIAGE_IT1 = 0 leaves it to the BP kernel
             b.it1_lut = (a.ms_scaling == 0.0 && a.max_iter >= 1 && g.opt_triage_it1)

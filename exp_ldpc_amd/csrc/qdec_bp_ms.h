@@ -79,9 +79,11 @@ __device__ __forceinline__ double max_abs2_f64(double a, double b) {
 // compares) and the variable pass flips a message's sign by the sign bit of the
 // v2c message it sent.  Both differ from the compares only through zero
 // entries, and a zero entry makes the row's m1 zero, so a row with m1 == 0
-// (rare; a divergent branch) takes the parity from the compares and gives m2
-// (the magnitude its zero entries select) the sign that makes the variable
-// side's sign bit test exact: the parity, flipped when the zeros are +0.  A
+// (a wave-uniform branch, taken while the row is still in registers: equal
+// priors send an exact +0 in iteration 1, so every listed shot meets one in
+// iteration 2) takes the parity from the compares and gives m2 (the magnitude
+// its zero entries select) the sign that makes the variable side's sign bit
+// test exact: the parity, flipped when the zeros are +0.  A
 // row holding both +0 and -0 has m2 = 0, where only the sign of a zero message
 // is left open, which changes no `<= 0` test, no magnitude and no hard
 // decision (only the sign of an exactly-zero posterior, which LEAN launches do
@@ -93,28 +95,6 @@ __device__ __forceinline__ double f64_xor_sign(double x, uint32_t m) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(x);
     const uint32_t hi = __builtin_amdgcn_bitop3_b32(m, (uint32_t)(b >> 32), 0x80000000u, 0x6c);
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | (uint32_t)b));
-}
-
-// The zero-row fix-up of the sign-bit check pass (a call: its registers stay
-// out of the BP loop's allocation).  `row`: the check's v2c row, `par`: its
-// syndrome bit, `sp`: its (m1, m2) state slot, written with the sign-bit parity.
-// m1's sign becomes the parity by ldpc's compares; m2 (the magnitude the row's
-// zero entries select) gets the parity flipped when those zeros are +0, so that
-// the variable side's sign-bit test gives parity ^ (v <= 0) for them too.
-using lds_f64 = __attribute__((address_space(3))) double;
-template <int DRC>
-__device__ __noinline__ void ms_zero_row_fix(lds_f64* row, bool par, lds_f64* sp) {
-    bool pz = false;
-#pragma unroll 1
-    for (int j = 0; j < DRC; ++j) {
-        const double w = row[j];
-        par ^= w <= 0.0;
-        pz |= __double_as_longlong(w) == 0ll;  // +0
-    }
-    const uint32_t hx = par ? 0x80000000u : 0u;
-    const uint32_t h2 = pz ? hx ^ 0x80000000u : hx;
-    sp[0] = f64_xor_sign(fabs(sp[0]), hx);
-    sp[1] = f64_xor_sign(fabs(sp[1]), h2);
 }
 
 // (smallest, second smallest) of |v[B]| .. |v[E-1]|, counted with multiplicity
@@ -298,10 +278,31 @@ struct MsCore {
                 if (!(rv < D3P && k == 3)) v2c[etab[rv][k] & 0xffff] = (rv % 2 == 0) ? L[rv / 2].x : L[rv / 2].y;
     }
 
-    // BP iterations it, it + 1, .. max_iter on rows holding the priors
-    // (write_priors, then a wave_lds_sync).  Returns true when the syndrome is
+    // the first check state from the host's table (ms_state0, qdec_tables.cpp:
+    // what the check pass writes for rows holding the priors, syndrome bit 0, by
+    // check lane), both signs flipped where the shot's syndrome bit is set
+    __device__ __forceinline__ static void load_state0(const DevGraph& g, int lane, V2 (&s0)[RC]) {
+        // scalar base + 32-bit lane offset (opaque here, so no per-lane address is
+        // formed ahead of the shot loop and kept in a VGPR pair across the BP loop)
+        const char* t = static_cast<const char*>(g.ms_state0[PREC]);
+        uint32_t off = (uint32_t)lane * (uint32_t)sizeof(V2);
+        asm volatile("" : "+v"(off));
+#pragma unroll
+        for (int rc = 0; rc < RC; ++rc) s0[rc] = *reinterpret_cast<const V2*>(t + off + rc * 64 * sizeof(V2));
+    }
+    __device__ __forceinline__ void write_state0(T* st, const V2 (&s0)[RC], const bool (&sbit)[RC]) const {
+#pragma unroll
+        for (int rc = 0; rc < RC; ++rc) *reinterpret_cast<V2*>(st + 2 * sslot[rc]) = sbit[rc] ? -s0[rc] : s0[rc];
+    }
+
+    // BP iterations it, it + 1, .. max_iter.  STATE0 = false: on rows holding
+    // the priors (write_priors, then a wave_lds_sync).  STATE0 = true (it = 1):
+    // on the first check state (write_state0, then a wave_lds_sync); iteration
+    // 1 has no check pass, and its variable pass, which sees the priors as the
+    // messages sent (vp), fills the rows.  Returns true when the syndrome is
     // met (`it` = that iteration); X: hard decisions by slot (ballot words),
     // pres: the residual syndrome bit of this lane's checks, Q: posteriors (!LEAN).
+    template <bool STATE0 = false>
     __device__ __forceinline__ bool iterate(const DecodeArgs& a, T* v2c, T* st, int m, int lane, const bool (&sbit)[RC],
                                             T (&Q)[RV], uint64_t (&X)[RV], bool (&pres)[RC], int& it) const {
         V2 vp[NP][kDC];  // v2c messages this lane sent last iteration, round pairs
@@ -311,65 +312,73 @@ struct MsCore {
             for (int k = 0; k < kDC; ++k) vp[p][k] = L[p];
         for (; it <= a.max_iter; ++it) {
             const T alpha = alpha_bits<T>(it, a.ms_scaling);
-            // ---- check pass: state (m1, m2) with the parity in both signs ----
-            uint32_t zrows = 0;  // rows holding a zero entry (sign-bit parity inexact)
+            // ---- check pass: state (m1, m2) with the parity in both signs
+            // (STATE0: iteration 1 starts from the table's state instead) ----
+            if (!STATE0 || it != 1) {
 #pragma unroll
-            for (int rc = 0; rc < RC; ++rc) {
-                const int i = min(rc * 64 + lane, m);  // pad check lanes share the Big row m
-                T v[kDR];
-                // odd f64 rows load only their DRC slots (r03i A/B: -0.5% BP kernel time)
-                if constexpr (sizeof(T) == 8 && DRC % 2 == 1) lds_load_first<T, DRC>(v2c + i * DRS, v);
-                else lds_load<T, kDR>(v2c + i * DRS, v);
-                T m1 = Big<T>::v, m2 = Big<T>::v;
-                bool par = sbit[rc];
-                if constexpr (sizeof(T) == 4) {
+                for (int rc = 0; rc < RC; ++rc) {
+                    const int i = min(rc * 64 + lane, m);  // pad check lanes share the Big row m
+                    T v[kDR];
+                    // odd f64 rows load only their DRC slots (r03i A/B: -0.5% BP kernel time)
+                    if constexpr (sizeof(T) == 8 && DRC % 2 == 1) lds_load_first<T, DRC>(v2c + i * DRS, v);
+                    else lds_load<T, kDR>(v2c + i * DRS, v);
+                    T m1 = Big<T>::v, m2 = Big<T>::v;
+                    bool par = sbit[rc];
+                    if constexpr (sizeof(T) == 4) {
 #pragma unroll
-                    for (int k = 0; k < DRC; ++k) {
-                        const T av = fabs(v[k]);
-                        m2 = med3(av, m1, m2);
-                        m1 = med3(av, m1, -Big<T>::v);  // true median = min(|v|, m1): one VALU, abs modifier
+                        for (int k = 0; k < DRC; ++k) {
+                            const T av = fabs(v[k]);
+                            m2 = med3(av, m1, m2);
+                            m1 = med3(av, m1, -Big<T>::v);  // true median = min(|v|, m1): one VALU, abs modifier
+                        }
+                    } else {
+                        // f64: (minimum, second minimum) of |v| by a merge tree instead of a
+                        // sequential chain (17 instead of 21 f64 ops for 7 values, depth 5
+                        // instead of 14); the same two values, so bit-identical
+                        const Top2 t = top2_tree<0, DRC>(v);
+                        m1 = t.lo;
+                        m2 = t.hi;
                     }
-                } else {
-                    // f64: (minimum, second minimum) of |v| by a merge tree instead of a
-                    // sequential chain (17 instead of 21 f64 ops for 7 values, depth 5
-                    // instead of 14); the same two values, so bit-identical
-                    const Top2 t = top2_tree<0, DRC>(v);
-                    m1 = t.lo;
-                    m2 = t.hi;
-                }
-                V2 s2;
-                if constexpr (SB) {
-                    // sign-canonical row: the parity is the XOR of the sign bits
-                    uint32_t hx = par ? 0x80000000u : 0u;
-                    int k = 0;
+                    V2 s2;
+                    if constexpr (SB) {
+                        // sign-canonical row: the parity is the XOR of the sign bits
+                        uint32_t hx = par ? 0x80000000u : 0u;
+                        int k = 0;
 #pragma unroll
-                    for (; k + 1 < DRC; k += 2) hx = __builtin_amdgcn_bitop3_b32(hx, f64_hi(v[k]), f64_hi(v[k + 1]), 0x96);
-                    if (k < DRC) hx ^= f64_hi(v[k]);
-                    // m1, m2 >= +0: the XOR of the parity bit sets their sign bit
-                    s2.x = f64_xor_sign(m1, hx);
-                    s2.y = f64_xor_sign(m2, hx);
-                    if (m1 == (T)0) zrows |= 1u << rc;  // a zero entry: fixed below
-                } else {
+                        for (; k + 1 < DRC; k += 2) hx = __builtin_amdgcn_bitop3_b32(hx, f64_hi(v[k]), f64_hi(v[k + 1]), 0x96);
+                        if (k < DRC) hx ^= f64_hi(v[k]);
+                        // m1, m2 >= +0: the XOR of the parity bit sets their sign bit
+                        s2.x = f64_xor_sign(m1, hx);
+                        s2.y = f64_xor_sign(m2, hx);
+                        // a row with a zero entry (wave-uniform test; the row is still in
+                        // registers): m1's sign is the parity by ldpc's compares; m2 (the
+                        // magnitude the row's zero entries select) gets the parity flipped
+                        // when those zeros are +0, so that the variable side's sign-bit
+                        // test gives parity ^ (v <= 0) for them too
+                        if (__ballot(s2.x == (T)0)) {
+                            if (s2.x == (T)0) {
+                                bool pz = false;
 #pragma unroll
-                    for (int k = 0; k < DRC; ++k)
-                        par ^= v[k] <= (T)0;  // ldpc: bit_to_check <= 0 flips the sign (s_xor of compare masks)
-                    // both minima carry the parity in their sign bit (they are >= +0)
-                    s2.x = par ? -m1 : m1;
-                    s2.y = par ? -m2 : m2;
+                                for (int j = 0; j < DRC; ++j) {
+                                    par ^= v[j] <= (T)0;
+                                    pz |= FBits<T>::to(v[j]) == 0;  // +0
+                                }
+                                s2.x = par ? -(T)0 : (T)0;
+                                s2.y = (par != pz) ? -fabs(s2.y) : fabs(s2.y);
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < DRC; ++k)
+                            par ^= v[k] <= (T)0;  // ldpc: bit_to_check <= 0 flips the sign (s_xor of compare masks)
+                        // both minima carry the parity in their sign bit (they are >= +0)
+                        s2.x = par ? -m1 : m1;
+                        s2.y = par ? -m2 : m2;
+                    }
+                    *reinterpret_cast<V2*>(st + 2 * sslot[rc]) = s2;
                 }
-                *reinterpret_cast<V2*>(st + 2 * sslot[rc]) = s2;
+                wave_lds_sync();
             }
-            if constexpr (SB) {
-                if (__ballot(zrows != 0u)) {  // rare (wave-uniform): rows with a zero entry, parity by the compares
-                    asm volatile("" ::: "memory");  // re-read the row and the state just written
-#pragma unroll
-                    for (int rc = 0; rc < RC; ++rc)
-                        if ((zrows >> rc) & 1u)
-                            ms_zero_row_fix<DRC>((lds_f64*)(v2c + min(rc * 64 + lane, m) * DRS), sbit[rc],
-                                                 (lds_f64*)(st + 2 * sslot[rc]));
-                }
-            }
-            wave_lds_sync();
 
             // ---- variable pass, rounds in pairs (the next pair's states are
             // gathered while this pair sums) ----
@@ -1197,6 +1206,8 @@ __device__ __forceinline__ int ssf_fused(const DevGraph& g, int max_steps, uint3
 // CmpEntry::kPer (one u64 per lane, the next chunk loaded while this one
 // decodes; a list shorter than kPer entries per wave is cut finer); chunks are
 // handed out by ShotSeq (static stride, then a counter for the tail).
+// A shot starts from the host's first check state (DevGraph::ms_state0) with
+// the syndrome's sign flips, not from rows of priors and a check pass over them.
 // FUSE (with DEFER): 0 = BP-failed shots go to the SSF queue; 1 / 2 = SSF runs
 // here (ssf_fused with RG = FUSE generators per lane).
 template <typename T, int RC, int RV, int DRC, bool DEFER, int D3R, int OCC = 0, int FUSE = 0>
@@ -1270,8 +1281,13 @@ __global__ __launch_bounds__(64, OCC > 0 ? OCC : (sizeof(T) == 4 ? 4 : 2)) void 
         const int64_t cnt = seg_cnt[v];
         ne_n = (int)min((int64_t)kp, cnt - c_in * kp);
         const int ps = v < kCmpSegs ? kCmpSegs + v : v - kCmpSegs;
-        const int64_t e = ((int64_t)ps * a.cmp_cap + c_in * kp) * EW + lane;
-        return lane < ne_n * EW ? __builtin_nontemporal_load(a.cmp + e) : 0ull;
+        // uniform entry address + 32-bit lane offset (opaque, so `a.cmp + lane` is
+        // not kept as a VGPR pair across the BP loop)
+        const int64_t e = ((int64_t)ps * a.cmp_cap + c_in * kp) * EW;
+        uint32_t lo = (uint32_t)lane * 8u;
+        asm volatile("" : "+v"(lo));
+        const char* src = reinterpret_cast<const char*>(a.cmp + e) + lo;
+        return lane < ne_n * EW ? __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(src)) : 0ull;
     };
     // one flat loop over this wave's entries (chunk c, entry q of it; the next
     // chunk cn is in flight in entn)
@@ -1288,6 +1304,11 @@ __global__ __launch_bounds__(64, OCC > 0 ? OCC : (sizeof(T) == 4 ? 4 : 2)) void 
     QDEC_STAMP(4);  // prologue
     while (c < nch) {
         {
+            // the first check state: loaded per shot (a few KB that stay in the
+            // caches; issued ahead of the entry's readlanes) and dead before the BP
+            // loop, so it costs the loop no registers
+            typename Core::V2 s0[RC];
+            Core::load_state0(g, lane, s0);
             const int64_t shot = (int64_t)readlane64(ent, q * EW);
             bool sbit[RC];
 #pragma unroll
@@ -1295,14 +1316,14 @@ __global__ __launch_bounds__(64, OCC > 0 ? OCC : (sizeof(T) == 4 ? 4 : 2)) void 
             uint64_t rpar[kMaxLogicalRounds];
 #pragma unroll
             for (int rr = 0; rr < kMaxLogicalRounds; ++rr) rpar[rr] = readlane64(ent, q * EW + 1 + RC + rr);
-            core.write_priors(v2c);
+            core.write_state0(st, s0, sbit);
             wave_lds_sync();
-            QDEC_STAMP(0);  // entry + initial messages
+            QDEC_STAMP(0);  // entry + first check state
             T Q[RV];
             uint64_t X[RV];
             bool pres[RC];
             int it = 1;
-            const bool conv = core.iterate(a, v2c, st, m, lane, sbit, Q, X, pres, it);
+            const bool conv = core.template iterate<true>(a, v2c, st, m, lane, sbit, Q, X, pres, it);
             const int iters = conv ? it : a.max_iter;
             QDEC_STAMP(1);  // BP iterations
             QDEC_COUNT(8, iters);
@@ -1362,7 +1383,9 @@ __global__ __launch_bounds__(64, OCC > 0 ? OCC : (sizeof(T) == 4 ? 4 : 2)) void 
                 }
 #pragma unroll
                 for (int rc = 0; rc < RC; ++rc) rw[rc] = __ballot(pres[rc]);
-                queue_push_packed<RV, RC>(a, shot, xw, rw, dw, lane);
+                int ql = lane;  // opaque: the queue's per-lane address is formed here, not kept across the BP loop
+                asm volatile("" : "+v"(ql));
+                queue_push_packed<RV, RC>(a, shot, xw, rw, dw, ql);
                 wave_lds_sync();
             } else {
                 int f = 0;

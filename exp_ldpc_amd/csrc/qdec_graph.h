@@ -88,6 +88,12 @@ struct DevGraph {
     const uint64_t* ms_smask;     // [n_pad/64][m_pad] slots of check i's columns inside 64-slot word w
     const uint16_t* ms_vslot;     // [n_pad] column held by lane slot s (pads: n_pad + s % 64)
     const void* ms_prior[2];      // [precision][n_pad] min-sum priors in slot order
+    // the check state (m1, m2) the first check pass of the compact kernel would
+    // write for check lane i (ms_sslot's order, pads included) on rows holding
+    // the priors under syndrome bit 0, in the kernel's precision and by its sign
+    // rule (ms_state0_table in qdec_tables.cpp); the kernel starts each listed
+    // shot from it instead of running that pass
+    const void* ms_state0[2];     // [precision][m_pad][2]
     int ms_d3r;                   // leading 64-slot rounds whose variables all have degree <= 3
     int ms_allpos;                // bit p: every prior LLR of precision p is > 0
     // iteration 1 of min-sum inside the triage (ms_triage_kernel, qdec_bp_ms.h):

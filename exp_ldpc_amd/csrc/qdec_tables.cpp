@@ -532,6 +532,45 @@ void it1_tables(HostGraph* G, bool pos64, const std::vector<double>& L64, bool p
     if (pos32) g.it1_lut[QD_F32] = G->prior_arena->upload(it1_lut<float>(G, L32, 1e30f));
 }
 
+// The first check state of the compact min-sum kernel (bp_ms_cmp_kernel,
+// DevGraph::ms_state0).  Before iteration 1 every v2c row holds its columns'
+// priors (Big in the unused positions), so what the first check pass writes
+// depends only on the priors and the check's syndrome bit, and the bit only
+// flips both signs.  Per check lane i (pads: an all-Big row) this is that pass
+// under syndrome bit 0, in the kernel's precision: m1 / m2 the two smallest
+// |prior| of the row counted with multiplicity (Big where the row has fewer;
+// the med3 chain and the top-2 tree select exactly these), both negated when
+// the row's parity (the count of priors <= 0, ldpc's sign test) is odd.
+// signbit_rule: the f64 kernel's sign-bit check pass, where a row with a zero
+// entry (m1 = 0) gives m2 the parity flipped when a zero is +0
+// (MsCore::iterate); rows without one have the same signs under both rules.
+template <typename T>
+std::vector<T> ms_state0_table(const HostGraph* G, const std::vector<T>& L, T big, bool signbit_rule) {
+    const DevGraph& g = G->dg;
+    std::vector<T> st(2 * (size_t)g.m_pad);
+    for (int i = 0; i < g.m_pad; ++i) {
+        T m1 = big, m2 = big;
+        bool par = false, pz = false;
+        if (i < g.m)
+            for (int e = G->row_ptr[i]; e < G->row_ptr[i + 1]; ++e) {
+                const T v = L[G->col_idx[e]];
+                const T av = std::fabs(v);
+                if (av < m1) {
+                    m2 = m1;
+                    m1 = av;
+                } else if (av < m2) {
+                    m2 = av;
+                }
+                par ^= v <= (T)0;
+                pz = pz || (v == (T)0 && !std::signbit(v));
+            }
+        const bool neg2 = par != (signbit_rule && m1 == (T)0 && pz);
+        st[2 * (size_t)i] = par ? -m1 : m1;
+        st[2 * (size_t)i + 1] = neg2 ? -m2 : m2;
+    }
+    return st;
+}
+
 // Row positions of the edges for the LDS-resident min-sum kernel
 // (bp_ms_lds_kernel): edge e of row i sits at LDS element i * kMlDRS + pos[e].
 // The check pass is independent of the order inside a row, so positions are
@@ -1108,6 +1147,7 @@ void set_priors(HostGraph* G, const double* probs) {
         for (auto& m2 : g.eprior)
             for (auto& q : m2) q = nullptr;
         g.ms_prior[QD_F64] = g.ms_prior[QD_F32] = nullptr;
+        g.ms_state0[QD_F64] = g.ms_state0[QD_F32] = nullptr;
         g.it1_vchk = g.it1_cvar = nullptr;
         g.it1_lut[QD_F64] = g.it1_lut[QD_F32] = nullptr;
         g.ms_allpos = 0;
@@ -1145,6 +1185,9 @@ void set_priors(HostGraph* G, const double* probs) {
         }
         g.ms_allpos = (pos64 ? 1 << QD_F64 : 0) | (pos32 ? 1 << QD_F32 : 0);
         it1_tables(G, pos64, ms64, pos32, ms32);
+        // the compact kernel is lean: f64 runs the sign-bit check pass, f32 the compares
+        g.ms_state0[QD_F64] = G->prior_arena->upload(ms_state0_table<double>(G, ms64, 1e308, true));
+        g.ms_state0[QD_F32] = G->prior_arena->upload(ms_state0_table<float>(G, ms32, 1e30f, false));
     }
     g.prior[QD_PRODUCT_SUM][QD_F64] = G->prior_arena->upload(ps64);
     g.prior[QD_PRODUCT_SUM][QD_F32] = G->prior_arena->upload(ps32);

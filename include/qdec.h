@@ -372,6 +372,14 @@ int qd_graph_plan(const qd_graph* g, const qd_params* p, int64_t B, uint32_t pre
  * vchk[n_pad] (the checks of column j's edges, 4 x u16, pad = m).  Fails when
  * the precision has no tables (a prior <= 0).  No reference counterpart. */
 int qd_graph_it1_tables_copy(const qd_graph* g, int32_t precision, uint16_t* lut, uint64_t* vchk, int32_t* n_pad);
+/* Host-only graphs: the first check state of the compact min-sum kernel,
+ * state[m_pad][2] of the precision's float type: the (m1, m2) pair check lane i
+ * writes in the first check pass (rows holding the priors, syndrome bit 0: the
+ * two smallest |prior| of the row, 1e308 / 1e30f where it has fewer, both
+ * negated on odd parity; f64 uses the sign-bit rule for rows holding a zero),
+ * and sslot[m_pad], the state slot of check lane i.  Either may be NULL.  -39
+ * when the graph has no wave shape or no BP priors.  No reference counterpart. */
+int qd_graph_ms_state0_copy(const qd_graph* g, int32_t precision, void* state, uint16_t* sslot, int32_t* m_pad);
 /* Host-only graphs: the f64 LDS-resident kernel's check-state slots (m64_layout):
  * etab uint16 [4][n] (slot of edge k of column j, 0xffff pad), check_of_slot
  * uint16 [m].  -38 when the graph has none.  For tests. */

@@ -7,8 +7,9 @@
 //   tables_check graph.bin      ->  "<FNV-1a digest, 16 hex digits> <table bytes>"
 //
 // It runs the build sequence of a host-only graph handle (tables, flip sets,
-// logicals, priors) on host sinks and prints what qd_graph_table_digest reports
-// for the same input (tests/test_tables_standalone.py compares the two).
+// logicals, priors with the iteration-1 and first-check-state tables) on host
+// sinks and prints what qd_graph_table_digest reports for the same input
+// (tests/test_tables_standalone.py compares the two).
 //
 // Input, little-endian: 10 x i32 header {m, n, n_data, fold_blocks, nnz, n_gen,
 // gen_nnz, k, lz_nnz, has_priors} (n_gen / k = -1: that call is skipped), then
