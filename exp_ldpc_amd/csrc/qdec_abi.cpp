@@ -289,6 +289,18 @@ void note_kernels(qd_graph* G) {
     G->last_pre = n.pre ? n.pre : "";
 }
 
+void put_name(const std::string& v, char* out, int32_t len) {
+    if (!out || len <= 0) return;
+    const size_t k = std::min(v.size(), (size_t)len - 1);
+    std::memcpy(out, v.data(), k);
+    out[k] = '\0';
+}
+
+// a stage whose instantiation the library does not build fails here, before anything is enqueued
+void check_plan(const DecodePlan& plan) {
+    if (plan.missing) throw Fail(-17, std::string("no built instantiation of the ") + plan.missing + " for this decode");
+}
+
 void attach_timing(qd_graph* G, DecodeArgs& a) {
     a.ev = nullptr;
     if (G->t_cap > 0 && G->t_count < G->t_cap) a.ev = &G->tev[(size_t)kTimingEvents * G->t_count++];
@@ -375,6 +387,7 @@ DecodeArgs make_args(const qd_graph* g, const qd_params* p, int64_t B, const uin
 // copies the results back on s right behind the launch.
 void enqueue_decode(qd_graph* G, const qd_params* p, DecodeArgs& a, hipStream_t s, bool allow_split) {
     const DecodePlan plan = plan_decode(G->dg, p->method, p->precision, a);
+    check_plan(plan);
     attach_queue(G, plan, a);
     attach_unpack(G, plan, a);
     attach_timing(G, a);
@@ -956,15 +969,9 @@ int qd_graph_last_kernels(qd_graph* G, char* bp, int32_t bp_len, char* ssf, int3
                           int32_t pre_len) {
     return guarded([&] {
         check_graph(G);
-        auto put = [](const std::string& v, char* out, int32_t len) {
-            if (!out || len <= 0) return;
-            const size_t k = std::min(v.size(), (size_t)len - 1);
-            std::memcpy(out, v.data(), k);
-            out[k] = '\0';
-        };
-        put(G->last_bp, bp, bp_len);
-        put(G->last_ssf, ssf, ssf_len);
-        put(G->last_pre, pre, pre_len);
+        put_name(G->last_bp, bp, bp_len);
+        put_name(G->last_ssf, ssf, ssf_len);
+        put_name(G->last_pre, pre, pre_len);
     });
 }
 
@@ -1038,37 +1045,55 @@ int qd_graph_queue_layout(const qd_graph* G, int64_t B, int64_t* out) {
     });
 }
 
+// the plan of a decode described by qd_graph_plan's inputs
+static DecodePlan plan_of(const qd_graph* G, const qd_params* p, int64_t B, uint32_t present) {
+    check_graph(G);
+    if (!p || B <= 0) throw Fail(-8, "null params or invalid batch");
+    if (p->method != QD_MIN_SUM && p->method != QD_PRODUCT_SUM) throw Fail(-3, "unknown BP method");
+    if (p->precision != QD_F32 && p->precision != QD_F64) throw Fail(-4, "unknown precision");
+    if (p->ssf && G->dg.n_gen <= 0) throw Fail(-6, "SSF requested but the graph has no flip sets");
+    // the planner reads only whether a buffer is present and how its rows
+    // are aligned: stand-in addresses, never dereferenced
+    const bool aligned = present & QD_PLAN_ROWS_ALIGNED;
+    auto in = [&](uint32_t bit) { return reinterpret_cast<uint8_t*>((present & bit) ? (aligned ? 64 : 65) : 0); };
+    auto io = [&](uint32_t bit) { return reinterpret_cast<uint8_t*>((present & bit) ? 64 : 0); };
+    DecodeArgs a{};
+    a.B = B;
+    a.max_iter = p->max_iter > 0 ? p->max_iter : G->dg.n;
+    a.ssf = p->ssf ? 1 : 0;
+    a.syn_flags = p->syn_flags & 3;
+    a.in_packed = (p->syn_flags & QD_INPUT_PACKED) ? 1 : 0;
+    a.ms_scaling = p->ms_scaling;
+    a.syn = in(QD_PLAN_SYN);
+    a.base = io(QD_PLAN_BASE);
+    a.readout = in(QD_PLAN_READOUT);
+    a.x_out = io(QD_PLAN_X);
+    a.corr_out = io(QD_PLAN_CORR);
+    a.llr_out = io(QD_PLAN_LLR);
+    a.fail = io(QD_PLAN_FAIL);
+    const DecodePlan plan = plan_decode(G->dg, p->method, p->precision, a);
+    check_plan(plan);
+    return plan;
+}
+
 int qd_graph_plan(const qd_graph* G, const qd_params* p, int64_t B, uint32_t present, int32_t* out) {
     return guarded([&] {
-        check_graph(G);
-        if (!p || B <= 0 || !out) throw Fail(-8, "null params, invalid batch or null output");
-        if (p->method != QD_MIN_SUM && p->method != QD_PRODUCT_SUM) throw Fail(-3, "unknown BP method");
-        if (p->precision != QD_F32 && p->precision != QD_F64) throw Fail(-4, "unknown precision");
-        if (p->ssf && G->dg.n_gen <= 0) throw Fail(-6, "SSF requested but the graph has no flip sets");
-        // the planner reads only whether a buffer is present and how its rows
-        // are aligned: stand-in addresses, never dereferenced
-        const bool aligned = present & QD_PLAN_ROWS_ALIGNED;
-        auto in = [&](uint32_t bit) { return reinterpret_cast<uint8_t*>((present & bit) ? (aligned ? 64 : 65) : 0); };
-        auto io = [&](uint32_t bit) { return reinterpret_cast<uint8_t*>((present & bit) ? 64 : 0); };
-        DecodeArgs a{};
-        a.B = B;
-        a.max_iter = p->max_iter > 0 ? p->max_iter : G->dg.n;
-        a.ssf = p->ssf ? 1 : 0;
-        a.syn_flags = p->syn_flags & 3;
-        a.in_packed = (p->syn_flags & QD_INPUT_PACKED) ? 1 : 0;
-        a.ms_scaling = p->ms_scaling;
-        a.syn = in(QD_PLAN_SYN);
-        a.base = io(QD_PLAN_BASE);
-        a.readout = in(QD_PLAN_READOUT);
-        a.x_out = io(QD_PLAN_X);
-        a.corr_out = io(QD_PLAN_CORR);
-        a.llr_out = io(QD_PLAN_LLR);
-        a.fail = io(QD_PLAN_FAIL);
-        const DecodePlan plan = plan_decode(G->dg, p->method, p->precision, a);
+        if (!out) throw Fail(-8, "null output");
+        const DecodePlan plan = plan_of(G, p, B, present);
         const int32_t v[8] = {plan.bp, plan.ssf, plan.two_pass, plan.expand_packed, plan.fuse, plan.q_rpar,
                               plan.placement,
                               plan.need_queue | plan.need_lists << 1 | plan.need_unpack << 2 | plan.need_scratch << 3};
         std::memcpy(out, v, sizeof(v));
+    });
+}
+
+int qd_graph_plan_names(const qd_graph* G, const qd_params* p, int64_t B, uint32_t present, char* bp, int32_t bp_len,
+                        char* ssf, int32_t ssf_len, char* pre, int32_t pre_len) {
+    return guarded([&] {
+        const DecodePlan plan = plan_of(G, p, B, present);
+        put_name(noted_name(plan.bp_k), bp, bp_len);
+        put_name(noted_name(plan.fin_k), ssf, ssf_len);
+        put_name(noted_name(plan.pre_k), pre, pre_len);
     });
 }
 

@@ -40,6 +40,7 @@
 
 #include "qdec_device.h"
 #include "qdec_bp_ms.h"
+#include "qdec_kernels.h"
 
 namespace qdec {
 
@@ -888,38 +889,116 @@ static size_t wave_lds_bytes(const DevGraph& g) {
            (size_t)g.n_pad + 64;
 }
 
-template <int RG, int XW, int RW>
-static int launch_ssf_wave(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream) {
-    // the fused failure check reads the dense logical table's LDS copy (as launch_bp_wave)
-    if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
-    const size_t lds = SsfLds<RG>::shared_bytes(g) + kSsfWaves * SsfLds<RG>::wave_bytes(g);
-    QDEC_NOTE_SSF("qdec::ssf_wave_kernel", RG, XW, RW);
-    return launch_resident(ssf_wave_kernel<RG, XW, RW>, 64 * kSsfWaves, lds, num_cus,
-                           (a.B + kSsfWaves - 1) / kSsfWaves /* queue length <= B */, stream, {}, g, a);
+// ---------------------------------------------------------------- kernel tables
+// Every instantiation of the wave-graph families this unit builds, one table
+// per family; entries are found by their template arguments (find_kernel).
+// Argument order of the entries' t[]:
+//   bp_wave_kernel    T, METHOD, RC, RV, DRC, DEFER
+//   bp_ms_wave_kernel T, RC, RV, DRC, DEFER, LEAN, D3R, OCC
+//   bp_ms_cmp_kernel  T, RC, RV, DRC, DEFER, D3R, OCC, FUSE
+//   ms_triage_kernel  RC, RV, PK
+//   ssf_wave_kernel   RG, XW, RW
+//   ssf_lut_kernel    RG, XW, RW, LEAN
+struct WaveTables {
+    KernelTable bp_wave, ms_wave, ms_cmp, triage, ssf_wave, ssf_lut;
+};
+
+// The rules that restrict the set (the tables are built by them, the plan picks
+// by them).  Every shape of QDEC_WAVE_SHAPES has every family; bp_wave_kernel
+// is built for product-sum only (min-sum has its own kernels).
+// D3R = 2 (two leading variable rounds of degree <= 3): only on shape (2, 4, 7),
+// the n = 225 HGP code with its 144 degree-3 columns
+constexpr bool wave_has_d3r2(int rc, int rv, int drc) { return rc == 2 && rv == 4 && drc == 7; }
+// OCC = 3 (three waves per SIMD): only for double with D3R = 2, and for the
+// one-pass kernel only with LEAN (the 168-VGPR build)
+constexpr bool wave_has_occ3(int precision, int d3r) { return precision == 0 && d3r == 2; }
+// FUSE (the table-driven SSF inside the compact kernel) only with DEFER
+
+template <typename T, int RC, int RV, int DRC, bool DEFER, bool LEAN, int D3R, int OCC>
+static void add_ms_wave(KernelTable& t) {
+    t.push_back(QDEC_INST(64, bp_ms_wave_kernel, T, RC, RV, DRC, DEFER, LEAN, D3R, OCC));
+    t.back().lds = [](const DevGraph& g, const DecodeArgs&) { return MsLds<T>::template bytes<RC, RV>(g); };
 }
 
-template <int RG, int XW, int RW, bool LEAN>
-static int launch_ssf_lut_t(const DevGraph& g, const DecodeArgs& a, int num_cus, hipStream_t stream) {
-    const size_t lds = SsfLutLds::shared_bytes(g) + kLutWaves * SsfLutLds::wave_bytes(g);
-    if (lds > 160 * 1024) return (int)hipErrorInvalidConfiguration;
-    QDEC_NOTE_SSF("qdec::ssf_lut_kernel", RG, XW, RW, LEAN);
-    return launch_resident(ssf_lut_kernel<RG, XW, RW, LEAN>, 64 * kLutWaves, lds, num_cus,
-                           (a.B + kLutWaves - 1) / kLutWaves /* queue length <= B */, stream, {}, g, a);
+template <typename T, int RC, int RV, int DRC, bool DEFER, int D3R, int OCC, int FUSE>
+static void add_ms_cmp(KernelTable& t) {
+    static_assert(DEFER || FUSE == 0, "FUSE only with DEFER");
+    t.push_back(QDEC_INST(64, bp_ms_cmp_kernel, T, RC, RV, DRC, DEFER, D3R, OCC, FUSE));
+    t.back().lds = [](const DevGraph& g, const DecodeArgs&) {
+        size_t b = MsLds<T>::core_bytes(g) + ((size_t)g.k * RV * 8 + 15) / 16 * 16 + 2 * kCmpLists * kCmpSegs * 8;
+        if (FUSE) b += ((size_t)RV * 8 + (size_t)g.m_pad * 2 + 15) / 16 * 16;  // fused SSF: xb, flog
+        return b;
+    };
 }
 
-template <int RG, int XW, int RW>
-static int launch_ssf_lut(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
-                          hipStream_t stream) {
-    if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
-    return p.ssf_lean ? launch_ssf_lut_t<RG, XW, RW, true>(g, a, num_cus, stream)
-                      : launch_ssf_lut_t<RG, XW, RW, false>(g, a, num_cus, stream);
+template <typename T, int RC, int RV, int DRC, bool DEFER, int D3R, int OCC>
+static void add_ms_occ(WaveTables& t) {
+    if constexpr (OCC == 0) add_ms_wave<T, RC, RV, DRC, DEFER, false, D3R, OCC>(t.ms_wave);
+    add_ms_wave<T, RC, RV, DRC, DEFER, true, D3R, OCC>(t.ms_wave);
+    add_ms_cmp<T, RC, RV, DRC, DEFER, D3R, OCC, 0>(t.ms_cmp);
+    if constexpr (DEFER) {
+        add_ms_cmp<T, RC, RV, DRC, DEFER, D3R, OCC, 1>(t.ms_cmp);
+        add_ms_cmp<T, RC, RV, DRC, DEFER, D3R, OCC, 2>(t.ms_cmp);
+    }
 }
 
-// one-wave BP blocks, each taking shots (or list chunks) until none are left
-template <typename K>
-static int launch_persistent(K kern, size_t lds, int num_cus, hipStream_t stream, const DevGraph& g,
-                             const DecodeArgs& a, int max_per_cu = 0) {
-    return launch_resident(kern, 64, lds, num_cus, a.B, stream, GridRule{max_per_cu, true}, g, a);
+template <typename T, int RC, int RV, int DRC, bool DEFER>
+static void add_bp_defer(WaveTables& t) {
+    t.bp_wave.push_back(QDEC_INST(64, bp_wave_kernel, T, 0, RC, RV, DRC, DEFER));
+    t.bp_wave.back().lds = [](const DevGraph& g, const DecodeArgs&) { return (wave_lds_bytes<T>(g) + 15) / 16 * 16; };
+    add_ms_occ<T, RC, RV, DRC, DEFER, 0, 0>(t);
+    if constexpr (wave_has_d3r2(RC, RV, DRC)) {
+        add_ms_occ<T, RC, RV, DRC, DEFER, 2, 0>(t);
+        if constexpr (wave_has_occ3(sizeof(T) == 4 ? 1 : 0, 2)) add_ms_occ<T, RC, RV, DRC, DEFER, 2, 3>(t);
+    }
+}
+
+template <int RC, int RV, bool PK>
+static void add_triage(KernelTable& t) {
+    t.push_back(QDEC_INST(64, ms_triage_kernel, RC, RV, PK));
+    // the logicals, the tile images (byte rows), the iteration-1 words (over
+    // the images; the kernel's layout, ms_triage_kernel)
+    t.back().lds = [](const DevGraph& g, const DecodeArgs& a) {
+        const bool want_fail = a.fail && a.readout && g.k > 0;
+        const size_t tiles = PK ? 0 : triage_img_bytes(64 * (int64_t)g.m) + triage_img_bytes(64 * (int64_t)g.n_data);
+        const size_t it1 = a.it1_lut ? TriageIt1<RC, RV>::bytes : 0;
+        return ((want_fail ? (size_t)g.k * g.lz_words * 8 : 0) + 15) / 16 * 16 + tiles + it1;
+    };
+}
+
+// the families that depend on the rounds only: the shapes share them ((2, 3, *), (2, 4, *))
+template <int RG, int RC, int RV>
+static void add_ssf(WaveTables& t) {
+    t.ssf_wave.push_back(QDEC_INST(64 * kSsfWaves, ssf_wave_kernel, RG, RV, RC));
+    t.ssf_wave.back().lds = [](const DevGraph& g, const DecodeArgs&) {
+        return SsfLds<RG>::shared_bytes(g) + kSsfWaves * SsfLds<RG>::wave_bytes(g);
+    };
+    t.ssf_lut.push_back(QDEC_INST(64 * kLutWaves, ssf_lut_kernel, RG, RV, RC, false));
+    t.ssf_lut.push_back(QDEC_INST(64 * kLutWaves, ssf_lut_kernel, RG, RV, RC, true));
+}
+
+template <int RC, int RV, int DRC>
+static void add_wave_shape(WaveTables& t) {
+    add_bp_defer<float, RC, RV, DRC, false>(t);
+    add_bp_defer<float, RC, RV, DRC, true>(t);
+    add_bp_defer<double, RC, RV, DRC, false>(t);
+    add_bp_defer<double, RC, RV, DRC, true>(t);
+    if (find_kernel(t.triage, {RC, RV, 0})) return;
+    add_triage<RC, RV, false>(t.triage);
+    add_triage<RC, RV, true>(t.triage);
+    add_ssf<1, RC, RV>(t);
+    add_ssf<2, RC, RV>(t);
+}
+
+static const WaveTables& wave_tables() {
+    static const WaveTables tables = [] {
+        WaveTables t;
+#define QDEC_SHAPE(R, V, D) add_wave_shape<R, V, D>(t);
+        QDEC_WAVE_SHAPES(QDEC_SHAPE)
+#undef QDEC_SHAPE
+        return t;
+    }();
+    return tables;
 }
 
 // ---------------------------------------------------------------- launch plan
@@ -968,6 +1047,35 @@ static void plan_decode_wave(const DevGraph& g, const DecodeArgs& a, DecodePlan&
                 : g.opt_ssf == kSsfScanNoSplit ? kFinScanNoSplit
                                                : kFinScan;
     }
+
+    // ---- the instantiation of every stage ----
+    const WaveTables& t = wave_tables();
+    const int rc = g.m_pad / 64, rv = g.n_pad / 64, drc = g.shape_drc;
+    const int defer = p.ssf != kFinNone;  // the BP kernels' DEFER (the fused SSF is compiled under it too)
+    if (p.method == 1) {
+        // f64: 2 waves per SIMD measured faster than 3 for a lone decode at every
+        // p (n = 225: 7.1 vs 9.3 ms per 2^18 shots at p = 0.1); concurrent
+        // decodes may ask for more (qd_graph_set_wave_occupancy)
+        p.wave_cap = g.wave_occ > 0 ? g.wave_occ : (p.precision == 0 ? 8 : 0);
+        const int d3r = wave_has_d3r2(rc, rv, drc) && g.ms_d3r >= 2 ? 2 : 0;
+        const bool occ3 = wave_has_occ3(p.precision, d3r) && p.wave_cap > 8;  // 3 waves per SIMD
+        if (p.two_pass) {
+            p.pre_k = find_kernel(t.triage, {rc, rv, a.in_packed && !p.expand_packed});
+            p.bp_k = find_kernel(t.ms_cmp, {p.precision, rc, rv, drc, defer, d3r, occ3 ? 3 : 0, p.fuse});
+            if (!p.pre_k) p.missing = "ms_triage_kernel";
+        } else {
+            p.bp_k = find_kernel(t.ms_wave, {p.precision, rc, rv, drc, defer, p.lean, d3r, occ3 && p.lean ? 3 : 0});
+        }
+    } else {
+        p.bp_k = find_kernel(t.bp_wave, {p.precision, 0, rc, rv, drc, defer});
+    }
+    if (!p.bp_k) p.missing = "wave BP kernel";
+    const int rg = g.n_gen <= 64 ? 1 : 2;
+    if (p.ssf == kFinLut) p.fin_k = find_kernel(t.ssf_lut, {rg, rv, rc, p.ssf_lean});
+    else if (p.ssf == kFinScan || p.ssf == kFinScanGather || p.ssf == kFinScanNoSplit)
+        p.fin_k = find_kernel(t.ssf_wave, {rg, rv, rc});
+    else if (p.ssf != kFinNone && p.ssf != kFinFused) p.fin_k = ssf_block_entry(p.ssf);
+    if (p.ssf != kFinNone && p.ssf != kFinFused && !p.fin_k) p.missing = "wave SSF kernel";
 }
 
 DecodePlan plan_decode(const DevGraph& g, int method, int precision, const DecodeArgs& a) {
@@ -983,8 +1091,7 @@ DecodePlan plan_decode(const DevGraph& g, int method, int precision, const Decod
     return p;
 }
 
-template <int RC, int RV>
-static int launch_triage(const DevGraph& g, const DecodeArgs& a, hipStream_t stream) {
+static int launch_triage(const DevGraph& g, const KernelEntry& k, const DecodeArgs& a, hipStream_t stream) {
     const bool want_fail = a.fail && a.readout && g.k > 0;
     // the tile loads are 16-B vector loads (packed rows: u64 loads); the list
     // counters take u64 atomics on their own 128-B lines, entries 16-B stores
@@ -994,155 +1101,90 @@ static int launch_triage(const DevGraph& g, const DecodeArgs& a, hipStream_t str
     if (!a.cmp || !a.cmp_count || (reinterpret_cast<uintptr_t>(a.cmp_count) & 127) ||
         (reinterpret_cast<uintptr_t>(a.cmp) & 15))
         return (int)hipErrorInvalidValue;
-    if (a.it1_lut && (!g.it1_vchk || !g.it1_cvar || g.m_pad != 64 * RC || g.n_pad != 64 * RV))
+    if (a.it1_lut && (!g.it1_vchk || !g.it1_cvar || g.m_pad != 64 * k.t[0] || g.n_pad != 64 * k.t[1]))
         return (int)hipErrorInvalidValue;
-    // the logicals, the tile images, the iteration-1 words (byte images: over
-    // the images; the kernel's layout, ms_triage_kernel)
-    const size_t tiles =
-        a.in_packed ? 0 : triage_img_bytes(64 * (int64_t)g.m) + triage_img_bytes(64 * (int64_t)g.n_data);
-    const size_t it1 = a.it1_lut ? TriageIt1<RC, RV>::bytes : 0;
-    const size_t lds = ((want_fail ? (size_t)g.k * g.lz_words * 8 : 0) + 15) / 16 * 16 +
-                       tiles + it1;
-    const void* fn = a.in_packed ? reinterpret_cast<const void*>(ms_triage_kernel<RC, RV, true>)
-                                 : reinterpret_cast<const void*>(ms_triage_kernel<RC, RV, false>);
+    const size_t lds = k.lds(g, a);
     if (lds > 64 * 1024) {  // large logical tables (k <= 256, lz_words <= 9)
-        const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t ea = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (ea != hipSuccess) return (int)ea;
     }
-    const dim3 grid((unsigned)((a.B + 63) / 64));
-    if (a.in_packed) {
-        QDEC_NOTE_PRE("qdec::ms_triage_kernel", RC, RV, true);
-        hipLaunchKernelGGL((ms_triage_kernel<RC, RV, true>), grid, dim3(64), lds, stream, g, a);
-    } else {
-        QDEC_NOTE_PRE("qdec::ms_triage_kernel", RC, RV, false);
-        hipLaunchKernelGGL((ms_triage_kernel<RC, RV, false>), grid, dim3(64), lds, stream, g, a);
-    }
-    return (int)hipGetLastError();
+    last_launch_names().pre = noted_name(&k);
+    return launch_entry(WaveSig{}, k, (a.B + 63) / 64, lds, stream, g, a);
 }
 
-// BP kernel of a wave shape: min-sum uses the compressed-state kernels, product-sum
-// the message-array kernel.
-template <typename T, int METHOD, int RC, int RV, int DRC, bool DEFER, int FUSE = 0>
+// one-wave BP blocks, each taking shots (or list chunks) until none are left
+static int launch_persistent(const KernelEntry& k, size_t lds, int num_cus, hipStream_t stream, const DevGraph& g,
+                             const DecodeArgs& a, int max_per_cu = 0) {
+    last_launch_names().bp = noted_name(&k);
+    return launch_entry_resident(WaveSig{}, k, lds, num_cus, a.B, stream, GridRule{max_per_cu, true}, g, a);
+}
+
+// The plan's BP stage on a wave graph: min-sum uses the compressed-state
+// kernels, product-sum the message-array kernel.
 static int launch_bp_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
                           hipStream_t stream, bool* triaged) {
-    if constexpr (METHOD == 1) {
-        // the fused failure check reads the dense logical table's LDS copy
-        // (lz_in_lds); wave-kernel graphs always have one (n <= 576)
-        if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
-        const size_t lds = MsLds<T>::template bytes<RC, RV>(g);
-        if (a.wave_ctr && !p.two_pass) {  // ShotSeq's chunk counter (two passes: the triage zeroes it)
-            const hipError_t e = hipMemsetAsync(a.wave_ctr, 0, sizeof(unsigned long long), stream);
-            if (e != hipSuccess) return (int)e;
-        }
-        const bool lean = p.lean;
-        // f64: 2 waves per SIMD measured faster than 3 for a lone decode at every
-        // p (n = 225: 7.1 vs 9.3 ms per 2^18 shots at p = 0.1); concurrent
-        // decodes may ask for more (qd_graph_set_wave_occupancy)
-        const int cap = g.wave_occ > 0 ? g.wave_occ : (sizeof(T) == 8 ? 8 : 0);
-        if (p.two_pass) {  // triage, then the listed shots
-            // the compact kernel starts every listed shot from the first check state
-            if (!g.ms_state0[sizeof(T) == 4 ? 1 : 0]) return (int)hipErrorInvalidValue;
-            DecodeArgs b = a;
-            b.cmp_zero_ok =(g.ms_allpos >> (sizeof(T) == 4 ? 1 : 0)) & 1;
-            // iteration 1 in the triage: the tables assume alpha_1 = 0.5 (the
-            // default schedule); QD_OPT_TRIAGE_IT1 = 0 leaves it to the BP kernel
-            b.it1_lut = (a.ms_scaling == 0.0 && a.max_iter >= 1 && g.opt_triage_it1)
-                            ? g.it1_lut[sizeof(T) == 4 ? 1 : 0]
-                            : nullptr;
-            if (!b.cmp_count_next) {  // double-buffered counters arrive zeroed (the previous triage)
-                const hipError_t e = hipMemsetAsync(b.cmp_count, 0, (size_t)kCmpLists * kCmpSegs * 128, stream);
-                if (e != hipSuccess) return (int)e;
-            }
-            int rc = launch_triage<RC, RV>(g, b, stream);
-            if (rc != 0) return rc;
-            *triaged = true;
-            if (b.ev) (void)hipEventRecord(b.ev[3], stream);  // end of the pre-pass
-            size_t clds = MsLds<T>::core_bytes(g) + ((size_t)g.k * RV * 8 + 15) / 16 * 16 +
-                          2 * kCmpLists * kCmpSegs * 8;
-            if (FUSE) clds += ((size_t)RV * 8 + (size_t)g.m_pad * 2 + 15) / 16 * 16;  // fused SSF: xb, flog
-            // a capped grid (f64: 8 waves per CU) must also be placed evenly: the
-            // dispatcher stacks up to the kernel's own occupancy on a CU (11 for
-            // the 159-VGPR f64 kernel) while others sit idle, so the LDS request is
-            // padded to 1/cap of the CU
-            if (cap > 0) clds = std::max(clds, (size_t)(160 * 1024 / cap) / 16 * 16);
-            // degree-3 rounds: the (2, 4, 7) shape instantiates D3R = 2 (n = 225 HGP: 144 degree-3 columns)
-            if constexpr (RC == 2 && RV == 4 && DRC == 7) {
-                if (g.ms_d3r >= 2) {
-                    if constexpr (sizeof(T) == 8) {
-                        if (cap > 8) {  // 3 waves per SIMD
-                            QDEC_NOTE_BP("qdec::bp_ms_cmp_kernel", tname<T>(), RC, RV, DRC, DEFER, 2, 3, FUSE);
-                            return launch_persistent(bp_ms_cmp_kernel<T, RC, RV, DRC, DEFER, 2, 3, FUSE>, clds,
-                                                     num_cus, stream, g, b, cap);
-                        }
-                    }
-                    QDEC_NOTE_BP("qdec::bp_ms_cmp_kernel", tname<T>(), RC, RV, DRC, DEFER, 2, 0, FUSE);
-                    return launch_persistent(bp_ms_cmp_kernel<T, RC, RV, DRC, DEFER, 2, 0, FUSE>, clds, num_cus,
-                                             stream, g, b, cap);
-                }
-            }
-            QDEC_NOTE_BP("qdec::bp_ms_cmp_kernel", tname<T>(), RC, RV, DRC, DEFER, 0, 0, FUSE);
-            return launch_persistent(bp_ms_cmp_kernel<T, RC, RV, DRC, DEFER, 0, 0, FUSE>, clds, num_cus, stream, g, b,
-                                     cap);
-        }
-        // degree-3 rounds: the (2, 4, 7) shape (n = 225 HGP: 144 degree-3 columns) instantiates D3R = 2
-        if constexpr (RC == 2 && RV == 4 && DRC == 7) {
-            if (g.ms_d3r >= 2) {
-                if constexpr (sizeof(T) == 8) {
-                    if (lean && cap > 8) {  // 3 waves per SIMD: the 168-VGPR build
-                        QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, true, 2, 3);
-                        return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, true, 2, 3>, lds, num_cus,
-                                                 stream, g, a, cap);
-                    }
-                }
-                if (lean) {
-                    QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, true, 2, 0);
-                    return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, true, 2>, lds, num_cus, stream,
-                                             g, a, cap);
-                }
-                QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, false, 2, 0);
-                return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, false, 2>, lds, num_cus, stream, g,
-                                         a, cap);
-            }
-        }
-        if (lean) {
-            QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, true, 0, 0);
-            return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, true, 0>, lds, num_cus, stream, g, a,
-                                     cap);
-        }
-        QDEC_NOTE_BP("qdec::bp_ms_wave_kernel", tname<T>(), RC, RV, DRC, DEFER, false, 0, 0);
-        return launch_persistent(bp_ms_wave_kernel<T, RC, RV, DRC, DEFER, false, 0>, lds, num_cus, stream, g, a, cap);
-    } else {
-        const size_t lds = (wave_lds_bytes<T>(g) + 15) / 16 * 16;
-        QDEC_NOTE_BP("qdec::bp_wave_kernel", tname<T>(), METHOD, RC, RV, DRC, DEFER);
-        return launch_persistent(bp_wave_kernel<T, METHOD, RC, RV, DRC, DEFER>, lds, num_cus, stream, g, a);
+    if (p.bp == kBpWave) return launch_persistent(*p.bp_k, p.bp_k->lds(g, a), num_cus, stream, g, a);
+    // the fused failure check reads the dense logical table's LDS copy
+    // (lz_in_lds); wave-kernel graphs always have one (n <= 576)
+    if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
+    if (a.wave_ctr && !p.two_pass) {  // ShotSeq's chunk counter (two passes: the triage zeroes it)
+        const hipError_t e = hipMemsetAsync(a.wave_ctr, 0, sizeof(unsigned long long), stream);
+        if (e != hipSuccess) return (int)e;
     }
+    const int cap = p.wave_cap;
+    if (!p.two_pass) return launch_persistent(*p.bp_k, p.bp_k->lds(g, a), num_cus, stream, g, a, cap);
+    // triage, then the listed shots
+    // the compact kernel starts every listed shot from the first check state
+    if (!g.ms_state0[p.precision]) return (int)hipErrorInvalidValue;
+    DecodeArgs b = a;
+    b.cmp_zero_ok = (g.ms_allpos >> p.precision) & 1;
+    // iteration 1 in the triage: the tables assume alpha_1 = 0.5 (the
+    // default schedule); QD_OPT_TRIAGE_IT1 = 0 leaves it to the BP kernel
+    b.it1_lut = (a.ms_scaling == 0.0 && a.max_iter >= 1 && g.opt_triage_it1) ? g.it1_lut[p.precision] : nullptr;
+    if (!b.cmp_count_next) {  // double-buffered counters arrive zeroed (the previous triage)
+        const hipError_t e = hipMemsetAsync(b.cmp_count, 0, (size_t)kCmpLists * kCmpSegs * 128, stream);
+        if (e != hipSuccess) return (int)e;
+    }
+    const int rc = launch_triage(g, *p.pre_k, b, stream);
+    if (rc != 0) return rc;
+    *triaged = true;
+    if (b.ev) (void)hipEventRecord(b.ev[3], stream);  // end of the pre-pass
+    size_t clds = p.bp_k->lds(g, b);
+    // a capped grid (f64: 8 waves per CU) must also be placed evenly: the
+    // dispatcher stacks up to the kernel's own occupancy on a CU (11 for
+    // the 159-VGPR f64 kernel) while others sit idle, so the LDS request is
+    // padded to 1/cap of the CU
+    if (cap > 0) clds = std::max(clds, (size_t)(160 * 1024 / cap) / 16 * 16);
+    return launch_persistent(*p.bp_k, clds, num_cus, stream, g, b, cap);
 }
 
-template <typename T, int METHOD, int RC, int RV, int DRC>
+static int launch_ssf_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                           hipStream_t stream) {
+    // the fused failure check reads the dense logical table's LDS copy (as launch_bp_wave)
+    if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
+    const KernelEntry& k = *p.fin_k;
+    const bool lut = p.ssf == kFinLut;
+    const int waves = lut ? kLutWaves : kSsfWaves;
+    const size_t lds = lut ? SsfLutLds::shared_bytes(g) + kLutWaves * SsfLutLds::wave_bytes(g) : k.lds(g, a);
+    if (lut && lds > 160 * 1024) return (int)hipErrorInvalidConfiguration;
+    last_launch_names().ssf = noted_name(&k);
+    return launch_entry_resident(WaveSig{}, k, lds, num_cus, (a.B + waves - 1) / waves /* queue length <= B */, stream,
+                                 {}, g, a);
+}
+
 static int launch_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a0, int num_cus, hipStream_t stream,
                        bool* triaged) {
     DecodeArgs a = a0;
     a.q_packed = p.q_packed;
     a.q_w = reinterpret_cast<uint64_t*>(a.q_x);
     a.q_rpar = p.q_rpar;
-    if (p.ssf == kFinNone) {
+    if (p.ssf != kFinNone && (!a.q_count || !a.q_idx || !a.q_x || !a.q_r)) return (int)hipErrorInvalidValue;
+    if (p.ssf == kFinNone || p.ssf == kFinFused) {  // the BP kernel finishes every shot
         record_ev(a, 0, stream);
-        const int rc = launch_bp_wave<T, METHOD, RC, RV, DRC, false>(g, p, a, num_cus, stream, triaged);
+        const int rc = launch_bp_wave(g, p, a, num_cus, stream, triaged);
         record_ev(a, 1, stream);
         record_ev(a, 2, stream);
         return rc;
-    }
-    if (!a.q_count || !a.q_idx || !a.q_x || !a.q_r) return (int)hipErrorInvalidValue;
-    if constexpr (METHOD == 1) {
-        if (p.ssf == kFinFused) {
-            record_ev(a, 0, stream);
-            const int rc = p.fuse == 1
-                               ? launch_bp_wave<T, METHOD, RC, RV, DRC, true, 1>(g, p, a, num_cus, stream, triaged)
-                               : launch_bp_wave<T, METHOD, RC, RV, DRC, true, 2>(g, p, a, num_cus, stream, triaged);
-            record_ev(a, 1, stream);
-            record_ev(a, 2, stream);
-            return rc;
-        }
     }
     if (!a.q_rpar) {  // the compact path's triage zeroes both counters itself (one launch fewer each)
         hipError_t e = hipMemsetAsync(a.q_count, 0, sizeof(int32_t), stream);
@@ -1151,7 +1193,7 @@ static int launch_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs&
         if (e != hipSuccess) return (int)e;
     }
     record_ev(a, 0, stream);
-    int rc = launch_bp_wave<T, METHOD, RC, RV, DRC, true>(g, p, a, num_cus, stream, triaged);
+    int rc = launch_bp_wave(g, p, a, num_cus, stream, triaged);
     record_ev(a, 1, stream);
     if (rc != 0) return rc;
     if (p.ssf == kFinIncBlock || p.ssf == kFinBlockLds) {  // generators the wave SSF kernels do not hold
@@ -1166,29 +1208,11 @@ static int launch_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs&
         if (e2 != hipSuccess) return (int)e2;
         ss = a.ssf_stream;
     }
-    if (p.ssf == kFinLut) {
-        rc = g.n_gen <= 64 ? launch_ssf_lut<1, RV, RC>(g, p, a, num_cus, ss)
-                           : launch_ssf_lut<2, RV, RC>(g, p, a, num_cus, ss);
-    } else {
-        DevGraph gs = g;  // QD_SSF_SCAN_GATHER: no incremental local syndromes
-        if (p.ssf == kFinScanGather) gs.g_inv = nullptr;
-        rc = g.n_gen <= 64 ? launch_ssf_wave<1, RV, RC>(gs, a, num_cus, ss)
-                           : launch_ssf_wave<2, RV, RC>(gs, a, num_cus, ss);
-    }
+    DevGraph gs = g;  // QD_SSF_SCAN_GATHER: no incremental local syndromes
+    if (p.ssf == kFinScanGather) gs.g_inv = nullptr;
+    rc = launch_ssf_wave(gs, p, a, num_cus, ss);
     record_ev(a, 2, ss);
     return rc;
-}
-
-template <typename T, int METHOD>
-static int dispatch_shape(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
-                          hipStream_t stream, bool* triaged) {
-    const int rc = g.m_pad / 64, rv = g.n_pad / 64;
-#define QDEC_SHAPE(R, V, D)                     \
-    if (rc == R && rv == V && g.shape_drc == D) \
-        return launch_wave<T, METHOD, R, V, D>(g, p, a, num_cus, stream, triaged);
-    QDEC_WAVE_SHAPES(QDEC_SHAPE)
-#undef QDEC_SHAPE
-    return (int)hipErrorNotSupported;
 }
 
 bool wave_kernel_supports(const DevGraph& g) {
@@ -1260,11 +1284,7 @@ int launch_decode(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a0, 
         a.in_packed = 0;
     }
     if (p.bp >= kBpGroup) return launch_decode_block(g, p, a, num_cus, stream, scratch, scratch_bytes);
-    if (p.precision == 1)
-        return p.method == 1 ? dispatch_shape<float, 1>(g, p, a, num_cus, stream, triaged)
-                             : dispatch_shape<float, 0>(g, p, a, num_cus, stream, triaged);
-    return p.method == 1 ? dispatch_shape<double, 1>(g, p, a, num_cus, stream, triaged)
-                         : dispatch_shape<double, 0>(g, p, a, num_cus, stream, triaged);
+    return launch_wave(g, p, a, num_cus, stream, triaged);
 }
 
 #ifdef QDEC_STAMPS

@@ -15,10 +15,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 
 #include "qdec_device.h"
+#include "qdec_kernels.h"
 
 namespace qdec {
 
@@ -1954,20 +1956,101 @@ int ssf_fin_path(const DevGraph& g, const DecodeArgs& a) {
                                                                                                 : kFinBlockLds;
 }
 
+// ---------------------------------------------------------------- kernel tables
+// Every instantiation of the workgroup families, one table per family (as
+// wave_tables of qdec_bp.hip).  Argument order of the entries' t[]:
+//   bp_block_kernel    T, METHOD, DEFER, DRM, DCM   (DRM = DCM = 0: loops over the degrees;
+//                                                    16, 8: unrolled, row degree <= 16, column degree <= 8)
+//   bp_group_kernel    T, METHOD, DR, DC            (DR in {8, 16} x DC in {4, 8}: the degrees it unrolls)
+//   bp_ms_lds_kernel   VPT                          (columns per thread)
+//   bp_ms_lds64_kernel VPT, D3R                     (D3R leading column rounds of degree <= 3)
+// The block SSF / finalize kernels are no templates: ssf[0] is
+// ssf_inc_block_kernel, ssf[1] ssf_block_kernel.  qd_graph_last_kernels does not
+// report bp_block_kernel or the block SSF kernels.
+struct BlockTables {
+    KernelTable block, group, lds, lds64, ssf;
+};
+using BlockSig = KernelSig<DevGraph, DecodeArgs, void*, int>;  // gscratch is T*
+using GroupSig = KernelSig<DevGraph, DecodeArgs, unsigned char*, size_t, const int32_t*, const int32_t*,
+                           const int32_t*, const int32_t*, const int32_t*, const void*, const void*>;  // priors: const T*
+using LdsSig = KernelSig<DevGraph, DecodeArgs, const uint16_t*, const float*, const float*>;
+using Lds64Sig = KernelSig<DevGraph, DecodeArgs, const uint16_t*, const double*, const uint16_t*,
+                           const unsigned long long*>;
+
+template <typename T, int METHOD>
+static void add_block_types(BlockTables& t) {
+    for (KernelEntry e : {QDEC_INST(kBlock, bp_block_kernel, T, METHOD, false, 0, 0),
+                          QDEC_INST(kBlock, bp_block_kernel, T, METHOD, true, 0, 0),
+                          QDEC_INST(kBlock, bp_block_kernel, T, METHOD, false, 16, 8),
+                          QDEC_INST(kBlock, bp_block_kernel, T, METHOD, true, 16, 8)}) {
+        e.noted = false;
+        t.block.push_back(e);
+    }
+    constexpr int kGrpThreads = 64 * grp_waves<T>();
+    t.group.push_back(QDEC_INST(kGrpThreads, bp_group_kernel, T, METHOD, 8, 4));
+    t.group.push_back(QDEC_INST(kGrpThreads, bp_group_kernel, T, METHOD, 8, 8));
+    t.group.push_back(QDEC_INST(kGrpThreads, bp_group_kernel, T, METHOD, 16, 4));
+    t.group.push_back(QDEC_INST(kGrpThreads, bp_group_kernel, T, METHOD, 16, 8));
+}
+
+static const BlockTables& block_tables() {
+    static const BlockTables tables = [] {
+        BlockTables t;
+        add_block_types<float, 0>(t);
+        add_block_types<float, 1>(t);
+        add_block_types<double, 0>(t);
+        add_block_types<double, 1>(t);
+        t.lds = {QDEC_INST(kMlThreads, bp_ms_lds_kernel, 4), QDEC_INST(kMlThreads, bp_ms_lds_kernel, 8),
+                 QDEC_INST(kMlThreads, bp_ms_lds_kernel, 10), QDEC_INST(kMlThreads, bp_ms_lds_kernel, 12),
+                 QDEC_INST(kMlThreads, bp_ms_lds_kernel, 16)};
+        t.lds64 = {QDEC_INST(kM64Threads, bp_ms_lds64_kernel, 4, 0),  QDEC_INST(kM64Threads, bp_ms_lds64_kernel, 8, 0),
+                   QDEC_INST(kM64Threads, bp_ms_lds64_kernel, 8, 4),  QDEC_INST(kM64Threads, bp_ms_lds64_kernel, 10, 0),
+                   QDEC_INST(kM64Threads, bp_ms_lds64_kernel, 10, 3), QDEC_INST(kM64Threads, bp_ms_lds64_kernel, 10, 6)};
+        KernelEntry inc, blk;
+        inc.fn = reinterpret_cast<const void*>(&ssf_inc_block_kernel);
+        inc.name = "qdec::ssf_inc_block_kernel";
+        blk.fn = reinterpret_cast<const void*>(&ssf_block_kernel);
+        blk.name = "qdec::ssf_block_kernel";
+        inc.block = blk.block = kBlock;
+        inc.noted = blk.noted = false;
+        t.ssf = {inc, blk};
+        return t;
+    }();
+    return tables;
+}
+
+const KernelEntry* ssf_block_entry(int path) {
+    const BlockTables& t = block_tables();
+    if (path == kFinIncBlock) return &t.ssf[0];
+    return path == kFinBlockLds || path == kFinBlockHbm ? &t.ssf[1] : nullptr;
+}
+
+// The LDS-resident kernels: the smallest built VPT that holds the graph's
+// columns (vpt per thread) and, with it, the largest built D3R <= the graph's
+// leading rounds of degree <= 3 (f64; the f32 kernel has no D3R)
+static const KernelEntry* pick_lds_kernel(const KernelTable& tab, int vpt, int d3r) {
+    const KernelEntry* best = nullptr;
+    for (const KernelEntry& e : tab) {
+        if (e.t[0] < vpt || (e.nt > 1 && e.t[1] > d3r)) continue;
+        if (!best || e.t[0] < best->t[0] || (e.t[0] == best->t[0] && e.nt > 1 && e.t[1] > best->t[1])) best = &e;
+    }
+    return best;
+}
+
 // the plan's SSF / finalize kernel; fin_state: the HBM shot state of kFinBlockHbm
 static int launch_ssf_fin(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
                           hipStream_t stream, unsigned char* fin_state = nullptr) {
     switch (p.ssf) {
         case kFinNone: return 0;
         case kFinIncBlock:
-            return launch_resident(ssf_inc_block_kernel, kBlock, ssf_inc_lds(g), num_cus, a.B, stream, {}, g, a);
+            return launch_entry_resident(WaveSig{}, *p.fin_k, ssf_inc_lds(g), num_cus, a.B, stream, {}, g, a);
         case kFinBlockLds:
-            return launch_resident(ssf_block_kernel, kBlock, (block_small_lds(g) + 15) / 16 * 16, num_cus, a.B, stream,
-                                   {}, g, a, (unsigned char*)nullptr);
+            return launch_entry_resident(KernelSig<DevGraph, DecodeArgs, unsigned char*>{}, *p.fin_k,
+                                         (block_small_lds(g) + 15) / 16 * 16, num_cus, a.B, stream, {}, g, a, nullptr);
         case kFinBlockHbm:
             if (!fin_state) return (int)hipErrorInvalidValue;
-            return launch_resident(ssf_block_kernel, kBlock, kCtrl, num_cus, a.B, stream, GridRule{kFinPerCu}, g, a,
-                                   fin_state);
+            return launch_entry_resident(KernelSig<DevGraph, DecodeArgs, unsigned char*>{}, *p.fin_k, kCtrl, num_cus,
+                                         a.B, stream, GridRule{kFinPerCu}, g, a, fin_state);
     }
     return (int)hipErrorNotSupported;
 }
@@ -1991,21 +2074,21 @@ static size_t fin_hbm_bytes(const DevGraph& g, const DecodePlan& p, int num_cus)
     return p.ssf == kFinBlockHbm ? (size_t)num_cus * kFinPerCu * block_state_stride(g) : 0;
 }
 
-template <typename T, int METHOD>
-static int launch_block_typed(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a0, int num_cus,
-                              hipStream_t stream, void* scratch, size_t scratch_bytes) {
-    const size_t msg = ((size_t)2 * g.E * sizeof(T) + 15) / 16 * 16;
+static int launch_block(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a0, int num_cus,
+                        hipStream_t stream, void* scratch, size_t scratch_bytes) {
+    const size_t tsz = p.precision == 1 ? 4 : 8;
+    const size_t msg = ((size_t)2 * g.E * tsz + 15) / 16 * 16;
     const size_t small = (block_small_lds(g) + 15) / 16 * 16;
     const int placement = p.placement;
     // placement 0: control area + the hard-decision bits of the unrolled kernel
     const size_t lds = (placement & 2) ? small + ((placement & 1) ? msg : 0) : kCtrl + (size_t)g.n_pad / 8;
     int cap = 0;
-    T* gs = nullptr;
+    void* gs = nullptr;
     DecodeArgs a = a0;
     const size_t fin_bytes = fin_hbm_bytes(g, p, num_cus);
     if (placement != 3) {
         // scratch = header (dynamic shot counter) + per-workgroup slices in HBM
-        const size_t per_wg = block_slice_bytes(g, sizeof(T), placement);
+        const size_t per_wg = block_slice_bytes(g, tsz, placement);
         if (!scratch || per_wg == 0 || scratch_bytes <= kGrpHeader + fin_bytes) return (int)hipErrorInvalidValue;
         const long long max_wg = (long long)((scratch_bytes - kGrpHeader - fin_bytes) / per_wg);
         // the grid is num_cus * cap workgroups, each owning one slice: at least
@@ -2021,20 +2104,14 @@ static int launch_block_typed(const DevGraph& g, const DecodePlan& p, const Deco
         if (placement == 0) cap = std::min(cap, 2);
         if (g.opt_block_wg > 0) cap = std::min((int)(max_wg / num_cus), g.opt_block_wg);
         a.work_ctr = static_cast<unsigned long long*>(scratch);
-        gs = reinterpret_cast<T*>(static_cast<unsigned char*>(scratch) + kGrpHeader);
+        gs = static_cast<unsigned char*>(scratch) + kGrpHeader;
         const hipError_t e0 = hipMemsetAsync(a.work_ctr, 0, sizeof(unsigned long long), stream);
         if (e0 != hipSuccess) return (int)e0;
     }
-    // graphs with row degree <= 16 and column degree <= 8: unrolled loops
-    const bool unr = g.max_rdeg <= 16 && g.max_cdeg <= 8;
-    constexpr int UR = 16, UC = 8;
     const GridRule rule{cap};
     if (p.ssf == kFinNone) {
         record_ev(a, 0, stream);
-        const int rc = unr ? launch_resident(bp_block_kernel<T, METHOD, false, UR, UC>, kBlock, lds, num_cus, a.B,
-                                             stream, rule, g, a, gs, placement)
-                           : launch_resident(bp_block_kernel<T, METHOD, false>, kBlock, lds, num_cus, a.B, stream, rule,
-                                             g, a, gs, placement);
+        const int rc = launch_entry_resident(BlockSig{}, *p.bp_k, lds, num_cus, a.B, stream, rule, g, a, gs, placement);
         record_ev(a, 1, stream);
         record_ev(a, 2, stream);
         return rc;
@@ -2043,10 +2120,7 @@ static int launch_block_typed(const DevGraph& g, const DecodePlan& p, const Deco
     hipError_t e = hipMemsetAsync(a.q_count, 0, sizeof(int32_t), stream);
     if (e != hipSuccess) return (int)e;
     record_ev(a, 0, stream);
-    int rc = unr ? launch_resident(bp_block_kernel<T, METHOD, true, UR, UC>, kBlock, lds, num_cus, a.B, stream, rule,
-                                   g, a, gs, placement)
-                 : launch_resident(bp_block_kernel<T, METHOD, true>, kBlock, lds, num_cus, a.B, stream, rule, g, a, gs,
-                                   placement);
+    int rc = launch_entry_resident(BlockSig{}, *p.bp_k, lds, num_cus, a.B, stream, rule, g, a, gs, placement);
     record_ev(a, 1, stream);
     if (rc != 0) return rc;
     rc = launch_ssf_fin(g, p, a, num_cus, stream,
@@ -2080,12 +2154,11 @@ static bool lds_kernel_applies(const DevGraph& g, const DecodePlan& p, const Dec
     return p.placement != 3;
 }
 
-template <int VPT>
-static int launch_lds_typed(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
-                            hipStream_t stream, float* img, size_t img_bytes) {
+static int launch_lds32(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                        hipStream_t stream, float* img, size_t img_bytes) {
     const size_t lds = ml_lds_bytes(g);
     long long grid = 0;
-    hipError_t e = resident_grid(bp_ms_lds_kernel<VPT>, kMlThreads, lds, num_cus, a.B, &grid);
+    hipError_t e = resident_grid(p.bp_k->fn, kMlThreads, lds, num_cus, a.B, &grid);
     if (e != hipSuccess) return (int)e;
     if (!img || img_bytes < ml_image_bytes(g)) return (int)hipErrorInvalidValue;
     e = hipMemsetAsync(a.wave_ctr, 0, sizeof(unsigned long long), stream);  // shot counter
@@ -2096,23 +2169,20 @@ static int launch_lds_typed(const DevGraph& g, const DecodePlan& p, const Decode
     hipLaunchKernelGGL(ml_init_check_kernel, dim3((unsigned)((g.m + 255) / 256)), dim3(256), 0, stream, g, img,
                        a.ms_scaling);
     record_ev(a, 0, stream);
-    QDEC_NOTE_BP("qdec::bp_ms_lds_kernel", VPT);
-    hipLaunchKernelGGL((bp_ms_lds_kernel<VPT>), dim3((unsigned)grid), dim3(kMlThreads), lds, stream, g, a, g.ml_etab,
-                       prior, img);
-    const hipError_t le = hipGetLastError();
+    last_launch_names().bp = noted_name(p.bp_k);
+    const int le = launch_entry(LdsSig{}, *p.bp_k, grid, lds, stream, g, a, g.ml_etab, prior, img);
     record_ev(a, 1, stream);
-    if (le != hipSuccess) return (int)le;
+    if (le != 0) return le;
     const int rc = launch_ssf_fin(g, p, a, num_cus, stream);
     record_ev(a, 2, stream);
     return rc;
 }
 
-template <int VPT, int D3R>
-static int launch_lds64_typed(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
-                              hipStream_t stream, unsigned long long* img, size_t img_bytes) {
+static int launch_lds64(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                        hipStream_t stream, unsigned long long* img, size_t img_bytes) {
     const size_t lds = m64_lds_bytes(g);
     long long grid = 0;
-    hipError_t e = resident_grid(bp_ms_lds64_kernel<VPT, D3R>, kM64Threads, lds, num_cus, a.B, &grid);
+    hipError_t e = resident_grid(p.bp_k->fn, kM64Threads, lds, num_cus, a.B, &grid);
     if (e != hipSuccess) return (int)e;
     e = hipMemsetAsync(a.wave_ctr, 0, sizeof(unsigned long long), stream);  // shot counter
     if (e != hipSuccess) return (int)e;
@@ -2121,12 +2191,10 @@ static int launch_lds64_typed(const DevGraph& g, const DecodePlan& p, const Deco
     hipLaunchKernelGGL(m64_init_kernel, dim3((unsigned)((g.m + 255) / 256)), dim3(256), 0, stream, g, prior,
                        g.m64_check, img);
     record_ev(a, 0, stream);
-    QDEC_NOTE_BP("qdec::bp_ms_lds64_kernel", VPT, D3R);
-    hipLaunchKernelGGL((bp_ms_lds64_kernel<VPT, D3R>), dim3((unsigned)grid), dim3(kM64Threads), lds, stream, g, a,
-                       g.m64_etab, prior, g.m64_check, img);
-    const hipError_t le = hipGetLastError();
+    last_launch_names().bp = noted_name(p.bp_k);
+    const int le = launch_entry(Lds64Sig{}, *p.bp_k, grid, lds, stream, g, a, g.m64_etab, prior, g.m64_check, img);
     record_ev(a, 1, stream);
-    if (le != hipSuccess) return (int)le;
+    if (le != 0) return le;
     const int rc = launch_ssf_fin(g, p, a, num_cus, stream);
     record_ev(a, 2, stream);
     return rc;
@@ -2134,26 +2202,11 @@ static int launch_lds64_typed(const DevGraph& g, const DecodePlan& p, const Deco
 
 static int launch_lds(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus, hipStream_t stream,
                       void* scratch, size_t scratch_bytes) {
-    unsigned long long* img = reinterpret_cast<unsigned long long*>(scratch);  // f64: iteration 1's states
     if (!a.q_count || !a.q_idx || !a.q_x || !a.q_r || !a.wave_ctr) return (int)hipErrorInvalidValue;
-    if (p.precision == 0) {
-        // the largest instantiated D3R <= the graph's (leading rounds of degree <= 3)
-        const int vpt = (g.n + kM64Threads - 1) / kM64Threads, d3r = g.m64_d3r;
-        if (vpt <= 4) return launch_lds64_typed<4, 0>(g, p, a, num_cus, stream, img, scratch_bytes);
-        if (vpt <= 8)
-            return d3r >= 4 ? launch_lds64_typed<8, 4>(g, p, a, num_cus, stream, img, scratch_bytes)
-                            : launch_lds64_typed<8, 0>(g, p, a, num_cus, stream, img, scratch_bytes);
-        if (d3r >= 6) return launch_lds64_typed<10, 6>(g, p, a, num_cus, stream, img, scratch_bytes);
-        if (d3r >= 3) return launch_lds64_typed<10, 3>(g, p, a, num_cus, stream, img, scratch_bytes);
-        return launch_lds64_typed<10, 0>(g, p, a, num_cus, stream, img, scratch_bytes);
-    }
-    float* fimg = reinterpret_cast<float*>(scratch);  // f32: iteration 1's c2v rows
-    const int vpt = (g.n + kMlThreads - 1) / kMlThreads;
-    if (vpt <= 4) return launch_lds_typed<4>(g, p, a, num_cus, stream, fimg, scratch_bytes);
-    if (vpt <= 8) return launch_lds_typed<8>(g, p, a, num_cus, stream, fimg, scratch_bytes);
-    if (vpt <= 10) return launch_lds_typed<10>(g, p, a, num_cus, stream, fimg, scratch_bytes);
-    if (vpt <= 12) return launch_lds_typed<12>(g, p, a, num_cus, stream, fimg, scratch_bytes);
-    return launch_lds_typed<16>(g, p, a, num_cus, stream, fimg, scratch_bytes);
+    if (p.precision == 0)  // f64: iteration 1's states
+        return launch_lds64(g, p, a, num_cus, stream, reinterpret_cast<unsigned long long*>(scratch), scratch_bytes);
+    // f32: iteration 1's c2v rows
+    return launch_lds32(g, p, a, num_cus, stream, reinterpret_cast<float*>(scratch), scratch_bytes);
 }
 
 // ---------------------------------------------------------------- slot-group launch
@@ -2167,40 +2220,26 @@ static size_t group_scratch_budget(const DevGraph& g) {
     return std::max<size_t>(free_b / 4, (size_t)64 << 20);
 }
 
-template <typename T, int METHOD, int DR, int DC>
-static int group_occupancy() {
-    static const int per_cu = [] {
-        int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, bp_group_kernel<T, METHOD, DR, DC>, 64 * grp_waves<T>(),
-                                                         0) != hipSuccess)
-            v = 1;
-        return std::max(v, 1);
-    }();
-    return per_cu;
-}
-
-// resident slot groups per CU of the instantiation launch_group_shape picks
-static int group_per_cu(const DevGraph& g, int method, size_t tsz) {
-    const bool r8 = g.max_rdeg <= 8, c4 = g.max_cdeg <= 4;
-#define QDEC_GOCC(T, M)                                                          \
-    return r8 ? (c4 ? group_occupancy<T, M, 8, 4>() : group_occupancy<T, M, 8, 8>()) \
-              : (c4 ? group_occupancy<T, M, 16, 4>() : group_occupancy<T, M, 16, 8>())
-    if (tsz == 4) {
-        if (method == 1) QDEC_GOCC(float, 1);
-        QDEC_GOCC(float, 0);
+// resident slot groups per CU of a bp_group_kernel entry (asked once per entry)
+static int group_per_cu(const KernelEntry& k) {
+    static std::atomic<int> per_cu[16];
+    std::atomic<int>& slot = per_cu[&k - block_tables().group.data()];
+    int v = slot.load(std::memory_order_relaxed);
+    if (v == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k.fn, k.block, 0) != hipSuccess) v = 1;
+        v = std::max(v, 1);
+        slot.store(v, std::memory_order_relaxed);
     }
-    if (method == 1) QDEC_GOCC(double, 1);
-    QDEC_GOCC(double, 0);
-#undef QDEC_GOCC
+    return v;
 }
 
-// Groups in flight: as many as the kernel's occupancy keeps resident, capped by
-// the scratch budget and by the batch (every slot should see >= 2 shots, so the
-// tail of a launch stays short and small test batches stay small).  The
-// scratch is sized from exactly this count (block_scratch_bytes).
-static int64_t group_count(const DevGraph& g, int method, size_t tsz, int num_cus, int64_t B) {
-    const size_t per = group_layout(g, tsz).total;
-    int64_t c = std::min<int64_t>((int64_t)num_cus * group_per_cu(g, method, tsz),
+// Groups in flight: as many as the planned kernel's occupancy keeps resident,
+// capped by the scratch budget and by the batch (every slot should see >= 2
+// shots, so the tail of a launch stays short and small test batches stay
+// small).  The scratch is sized from exactly this count (block_scratch_bytes).
+static int64_t group_count(const DevGraph& g, const DecodePlan& p, int num_cus, int64_t B) {
+    const size_t per = group_layout(g, p.precision == 1 ? 4 : 8).total;
+    int64_t c = std::min<int64_t>((int64_t)num_cus * group_per_cu(*p.bp_k),
                                   (int64_t)(group_scratch_budget(g) / per));
     c = std::min<int64_t>(c, (B + 127) / 128);
     return std::max<int64_t>(c, 1);
@@ -2219,19 +2258,18 @@ static bool group_kernel_applies(const DevGraph& g, const DecodePlan& p, const D
     return p.placement != 3;
 }
 
-template <typename T, int METHOD, int DR, int DC>
-static int launch_group_typed(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
-                              hipStream_t stream, void* scratch, size_t scratch_bytes) {
-    const size_t gb = group_layout(g, sizeof(T)).total;
+static int launch_group(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
+                        hipStream_t stream, void* scratch, size_t scratch_bytes) {
+    const size_t gb = group_layout(g, p.precision == 1 ? 4 : 8).total;
     const size_t fin_bytes = fin_hbm_bytes(g, p, num_cus);
     if (!scratch || scratch_bytes < fin_bytes + kGrpHeader + gb) return (int)hipErrorOutOfMemory;
     unsigned char* base = static_cast<unsigned char*>(scratch);
     unsigned char* fin_state = fin_bytes ? base + (scratch_bytes - fin_bytes) : nullptr;
     const int64_t max_groups = (int64_t)((scratch_bytes - fin_bytes - kGrpHeader) / gb);
-    constexpr int kGrpThreads = 64 * grp_waves<T>();
+    const KernelEntry& k = *p.bp_k;
     long long grid = 0;
-    hipError_t e = resident_grid(bp_group_kernel<T, METHOD, DR, DC>, kGrpThreads, 0, num_cus,
-                                 std::min<int64_t>(max_groups, group_count(g, METHOD, sizeof(T), num_cus, a.B)), &grid);
+    hipError_t e = resident_grid(k.fn, k.block, 0, num_cus,
+                                 std::min<int64_t>(max_groups, group_count(g, p, num_cus, a.B)), &grid);
     if (e != hipSuccess) return (int)e;
     if (grid <= 0) return (int)hipErrorOutOfMemory;
     e = hipMemsetAsync(base, 0, sizeof(unsigned long long), stream);  // shot counter
@@ -2242,27 +2280,14 @@ static int launch_group_typed(const DevGraph& g, const DecodePlan& p, const Deco
         if (e != hipSuccess) return (int)e;
     }
     record_ev(a, 0, stream);
-    QDEC_NOTE_BP("qdec::bp_group_kernel", tname<T>(), METHOD, DR, DC);
-    hipLaunchKernelGGL((bp_group_kernel<T, METHOD, DR, DC>), dim3((unsigned)grid), dim3(kGrpThreads), 0, stream, g, a,
-                       base, gb, g.row_ptr, g.col_idx, g.col_ptr, g.col_edge, g.edge_csc,
-                       reinterpret_cast<const T*>(g.prior[METHOD][sizeof(T) == 4 ? 1 : 0]),
-                       reinterpret_cast<const T*>(g.eprior[METHOD][sizeof(T) == 4 ? 1 : 0]));
-    const hipError_t le = hipGetLastError();
+    last_launch_names().bp = noted_name(&k);
+    const int le = launch_entry(GroupSig{}, k, grid, 0, stream, g, a, base, gb, g.row_ptr, g.col_idx, g.col_ptr,
+                                g.col_edge, g.edge_csc, g.prior[p.method][p.precision], g.eprior[p.method][p.precision]);
     record_ev(a, 1, stream);
-    if (le != hipSuccess) return (int)le;
+    if (le != 0) return le;
     const int rc = launch_ssf_fin(g, p, a, num_cus, stream, fin_state);
     record_ev(a, 2, stream);
     return rc;
-}
-
-template <typename T, int METHOD>
-static int launch_group_shape(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
-                              hipStream_t stream, void* scratch, size_t scratch_bytes) {
-    const bool r8 = g.max_rdeg <= 8, c4 = g.max_cdeg <= 4;
-    if (r8) return c4 ? launch_group_typed<T, METHOD, 8, 4>(g, p, a, num_cus, stream, scratch, scratch_bytes)
-                      : launch_group_typed<T, METHOD, 8, 8>(g, p, a, num_cus, stream, scratch, scratch_bytes);
-    return c4 ? launch_group_typed<T, METHOD, 16, 4>(g, p, a, num_cus, stream, scratch, scratch_bytes)
-              : launch_group_typed<T, METHOD, 16, 8>(g, p, a, num_cus, stream, scratch, scratch_bytes);
 }
 
 // The workgroup half of plan_decode.  The slot-group kernel has precedence over
@@ -2277,6 +2302,22 @@ void plan_decode_block(const DevGraph& g, const DecodeArgs& a, DecodePlan& p) {
     p.ssf = !a.ssf && p.bp != kBpLds ? kFinNone : p.placement == 0 ? kFinBlockHbm : ssf_fin_path(g, a);
     p.expand_packed = a.in_packed != 0;
     p.need_scratch = p.bp != kBpBlock || p.placement != 3;
+
+    // ---- the instantiation of every stage ----
+    const BlockTables& t = block_tables();
+    if (p.bp == kBpGroup) {
+        p.bp_k = find_kernel(t.group, {p.precision, p.method, g.max_rdeg <= 8 ? 8 : 16, g.max_cdeg <= 4 ? 4 : 8});
+    } else if (p.bp == kBpLds) {
+        p.bp_k = p.precision == 0
+                     ? pick_lds_kernel(t.lds64, (g.n + kM64Threads - 1) / kM64Threads, g.m64_d3r)
+                     : pick_lds_kernel(t.lds, (g.n + kMlThreads - 1) / kMlThreads, 0);
+    } else {
+        // graphs with row degree <= 16 and column degree <= 8: unrolled loops
+        const bool unr = g.max_rdeg <= 16 && g.max_cdeg <= 8;
+        p.bp_k = find_kernel(t.block, {p.precision, p.method, p.ssf != kFinNone, unr ? 16 : 0, unr ? 8 : 0});
+    }
+    p.fin_k = ssf_block_entry(p.ssf);
+    if (!p.bp_k) p.missing = "workgroup BP kernel";
 }
 
 size_t block_scratch_bytes(const DevGraph& g, const DecodePlan& p, int num_cus, const DecodeArgs& a) {
@@ -2284,7 +2325,7 @@ size_t block_scratch_bytes(const DevGraph& g, const DecodePlan& p, int num_cus, 
     const size_t fin = fin_hbm_bytes(g, p, num_cus);
     switch (p.bp) {
         case kBpGroup:
-            return kGrpHeader + (size_t)group_count(g, p.method, tsz, num_cus, a.B) * group_layout(g, tsz).total + fin;
+            return kGrpHeader + (size_t)group_count(g, p, num_cus, a.B) * group_layout(g, tsz).total + fin;
         case kBpLds:
             // iteration 1's image (f64: check states, m64_init_kernel; f32: c2v rows, ml_init_*_kernel)
             return p.precision == 0 ? m64_image_bytes(g) : ml_image_bytes(g);
@@ -2311,18 +2352,11 @@ int launch_decode_block(const DevGraph& g, const DecodePlan& p, const DecodeArgs
                         hipStream_t stream, void* scratch, size_t scratch_bytes) {
     if (a.B <= 0) return 0;
     if (a.ssf && g.n_gen <= 0) return (int)hipErrorInvalidValue;
-#define QDEC_BLOCK_TYPES(F)                                                                             \
-    if (p.precision == 1)                                                                               \
-        return p.method == 1 ? F<float, 1>(g, p, a, num_cus, stream, scratch, scratch_bytes)            \
-                             : F<float, 0>(g, p, a, num_cus, stream, scratch, scratch_bytes);           \
-    return p.method == 1 ? F<double, 1>(g, p, a, num_cus, stream, scratch, scratch_bytes)               \
-                         : F<double, 0>(g, p, a, num_cus, stream, scratch, scratch_bytes);
     switch (p.bp) {
-        case kBpGroup: QDEC_BLOCK_TYPES(launch_group_shape)
+        case kBpGroup: return launch_group(g, p, a, num_cus, stream, scratch, scratch_bytes);
         case kBpLds: return launch_lds(g, p, a, num_cus, stream, scratch, scratch_bytes);
-        case kBpBlock: QDEC_BLOCK_TYPES(launch_block_typed)
+        case kBpBlock: return launch_block(g, p, a, num_cus, stream, scratch, scratch_bytes);
     }
-#undef QDEC_BLOCK_TYPES
     return (int)hipErrorNotSupported;
 }
 

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -111,46 +113,40 @@ inline void record_ev(const DecodeArgs& a, int i, hipStream_t s) {
     if (i == 0) (void)hipEventRecord(a.ev[3], s);
 }
 
+// One built instantiation of a kernel family: what a launch needs to know about
+// it.  The families' tables (wave_tables in qdec_bp.hip, block_tables in
+// qdec_bp_block.hip) list every instantiation the library builds; plan_decode
+// picks the entries of a decode, the launchers launch what the plan holds.
+struct KernelEntry {
+    const void* fn = nullptr;  // host address of the kernel (hipLaunchKernel, hipFuncSetAttribute)
+    std::string name;          // rocprofv3's spelling: base<arg, arg, ...>
+    int t[8] = {};             // the template arguments in the kernel's order (types: QD_F64 / QD_F32)
+    int nt = 0;
+    int block = 0;             // threads per workgroup
+    bool noted = true;         // qd_graph_last_kernels reports the stage (false: it stays "")
+    // dynamic LDS of a launch, for the families whose size depends on template
+    // arguments (before the launcher's padding); nullptr: the launcher's own figure
+    size_t (*lds)(const DevGraph&, const DecodeArgs&) = nullptr;
+};
+using KernelTable = std::vector<KernelEntry>;
+// the entry with exactly these template arguments, nullptr when it is not built
+inline const KernelEntry* find_kernel(const KernelTable& tab, std::initializer_list<int> targs) {
+    for (const KernelEntry& e : tab)
+        if ((size_t)e.nt == targs.size() && std::equal(targs.begin(), targs.end(), e.t)) return &e;
+    return nullptr;
+}
+
 // Names of the BP and SSF kernels the calling host thread's last launch_decode
 // enqueued, spelled as rocprofv3 prints them (template arguments included; ""
-// when none / not recorded).  Host only; read by qd_graph_last_kernels.
+// when none / not recorded): the names of the plan's entries, noted as each
+// stage is enqueued.  Host only; read by qd_graph_last_kernels.
 struct LaunchNames {
     const char* bp = "";
     const char* ssf = "";
     const char* pre = "";  // a pass before the BP kernel (ms_triage_kernel), inside the BP timing
 };
 LaunchNames& last_launch_names();
-
-// rocprofv3's spelling of a kernel instantiation: base<arg, arg, ...>
-inline std::string targ(bool b) { return b ? "true" : "false"; }
-inline std::string targ(int v) { return std::to_string(v); }
-inline std::string targ(const char* s) { return s; }
-template <typename T>
-inline const char* tname() { return sizeof(T) == 8 ? "double" : "float"; }
-template <typename... A>
-inline std::string kernel_name(const char* base, A... args) {
-    std::string s = std::string(base) + "<";
-    bool first = true;
-    ((s += (first ? std::string() : std::string(", ")) + targ(args), first = false), ...);
-    return s + ">";
-}
-// record the instantiation (one string per call site and instantiation)
-#define QDEC_NOTE_BP(...)                                           \
-    do {                                                            \
-        static const std::string qdec_kn_ = kernel_name(__VA_ARGS__); \
-        last_launch_names().bp = qdec_kn_.c_str();                  \
-    } while (0)
-#define QDEC_NOTE_PRE(...)                                          \
-    do {                                                            \
-        static const std::string qdec_kn_ = kernel_name(__VA_ARGS__); \
-        last_launch_names().pre = qdec_kn_.c_str();                 \
-    } while (0)
-#define QDEC_NOTE_SSF(...)                                          \
-    do {                                                            \
-        static const std::string qdec_kn_ = kernel_name(__VA_ARGS__); \
-        last_launch_names().ssf = qdec_kn_.c_str();                 \
-    } while (0)
-
+inline const char* noted_name(const KernelEntry* e) { return e && e->noted ? e->name.c_str() : ""; }
 
 // ---------------------------------------------------------------- launch plan
 // Everything a decode decides before its first launch, decided once
@@ -187,6 +183,14 @@ struct DecodePlan {
     int q_packed, q_rpar;  // DecodeArgs' queue flags
     bool ssf_lean;       // ssf_lut_kernel's LEAN instantiation
     bool expand_packed;  // packed inputs go through unpack_rows_kernel first
+    int wave_cap;        // wave min-sum: waves per CU the launch is capped to (0: the kernel's occupancy)
+    // the instantiation of every stage (entries of the families' tables):
+    // pre-pass (two_pass), BP, SSF / finalize (nullptr: no such stage)
+    const KernelEntry* pre_k;
+    const KernelEntry* bp_k;
+    const KernelEntry* fin_k;
+    // a stage's instantiation is not built: the family's name (nullptr: the plan is complete)
+    const char* missing;
     // library-owned buffers the launch needs
     bool need_queue, need_lists, need_unpack, need_scratch;
 };
@@ -198,6 +202,8 @@ DecodePlan plan_decode(const DevGraph& g, int method, int precision, const Decod
 void plan_decode_block(const DevGraph& g, const DecodeArgs& a, DecodePlan& p);
 // SSF + finalize of queued shots by a workgroup kernel with its state in LDS
 int ssf_fin_path(const DevGraph& g, const DecodeArgs& a);
+// the workgroup SSF / finalize kernel of a path (kFinIncBlock, kFinBlockLds, kFinBlockHbm)
+const KernelEntry* ssf_block_entry(int path);
 bool wave_kernel_supports(const DevGraph& g);
 // byte rows of expanded packed inputs: the regions of unpack_buf (16-B aligned,
 // so the byte-row triage can load them)

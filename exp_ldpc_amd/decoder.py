@@ -384,6 +384,19 @@ class Decoder:
                    "qd_graph_last_kernels")
         return bp.value.decode(), ssf.value.decode(), pre.value.decode()
 
+    def planned_kernels(self, B: int, *, present=("syn", "readout", "fail"), aligned: bool = True,
+                        ssf: bool | None = None, packed: bool = False) -> tuple[str, str, str]:
+        """What last_kernels() returns after a decode of B shots passing the
+        optional buffers named in `present` (syn, base, readout, x, corr, llr,
+        fail), by the launch plan alone (qd_graph_plan_names): no launch."""
+        bits = {"syn": 1, "base": 2, "readout": 4, "x": 8, "corr": 16, "llr": 32, "fail": 64}
+        mask = sum(bits[name] for name in present) | (128 if aligned else 0)
+        prm = self._params(QD_INPUT_PACKED if packed else 0, ssf)
+        bp, fin, pre = (C.create_string_buffer(512) for _ in range(3))
+        _abi.check(self._lib.qd_graph_plan_names(self._handle, C.byref(prm), int(B), mask, bp, 512, fin, 512, pre, 512),
+                   "qd_graph_plan_names")
+        return bp.value.decode(), fin.value.decode(), pre.value.decode()
+
     def close(self) -> None:
         if getattr(self, "_handle", None) and self._handle.value:
             self._lib.qd_graph_destroy(self._handle)

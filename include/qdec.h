@@ -365,6 +365,14 @@ int qd_graph_queue_layout(const qd_graph* g, int64_t B, int64_t* out);
 #define QD_FIN_BLOCK_LDS 7      /* ssf_block_kernel, shot state in LDS */
 #define QD_FIN_BLOCK_HBM 8      /* ssf_block_kernel, shot state in HBM */
 int qd_graph_plan(const qd_graph* g, const qd_params* p, int64_t B, uint32_t present, int32_t* out);
+/* The instantiations that plan holds, by name: the three strings
+ * qd_graph_last_kernels returns after the same decode (the plan picks every
+ * stage's entry of the kernel tables, the launchers record what they enqueue
+ * from it), also on host-only graphs.  A decode whose instantiation the library
+ * does not build fails here and in qd_graph_plan with -17.  No reference
+ * counterpart. */
+int qd_graph_plan_names(const qd_graph* g, const qd_params* p, int64_t B, uint32_t present, char* bp,
+                        int32_t bp_len, char* ssf, int32_t ssf_len, char* pre, int32_t pre_len);
 
 /* Copies of the triage's iteration-1 tables (host-only graphs): lut[n_pad]
  * (bit b = column j's hard decision after min-sum iteration 1 under syndrome

@@ -518,8 +518,20 @@ PLAN_FIN = {0: "", 1: "", 2: "qdec::ssf_lut_kernel", 3: "qdec::ssf_wave_kernel",
             5: "qdec::ssf_wave_kernel", 6: "", 7: "", 8: ""}
 
 
+def _plan_names(lib, h, prm, B, present):
+    """(bp, ssf, pre) of qd_graph_plan_names."""
+    import ctypes as C
+
+    from exp_ldpc_amd import _abi
+    bufs = [C.create_string_buffer(512) for _ in range(3)]
+    _abi.check(lib.qd_graph_plan_names(h, C.byref(prm), B, present, bufs[0], 512, bufs[1], 512, bufs[2], 512),
+               "qd_graph_plan_names")
+    return [b.value.decode() for b in bufs]
+
+
 def _plan(lib, h, row, B=128):
-    """qd_graph_plan for a tools/record_dispatch.py row on host graph h."""
+    """qd_graph_plan and qd_graph_plan_names (key "names") for a
+    tools/record_dispatch.py row on host graph h."""
     import ctypes as C
 
     from exp_ldpc_amd import _abi
@@ -536,8 +548,10 @@ def _plan(lib, h, row, B=128):
         (0 if row["misaligned"] else PLAN_ALIGNED)
     out = np.zeros(8, np.int32)
     _abi.check(lib.qd_graph_plan(h, C.byref(prm), B, present, _abi.ptr(out)), "qd_graph_plan")
-    return dict(zip(("bp", "fin", "two_pass", "expand_packed", "fuse", "q_rpar", "placement", "buffers"),
+    plan = dict(zip(("bp", "fin", "two_pass", "expand_packed", "fuse", "q_rpar", "placement", "buffers"),
                     (int(v) for v in out)))
+    plan["names"] = _plan_names(lib, h, prm, B, present)
+    return plan
 
 
 def _check_plan_against_names(row, plan, names):
@@ -572,18 +586,22 @@ def _check_plans_of(graphs):
             rows = rd.rows_of([name])
             assert rows
             for row in rows:
-                _check_plan_against_names(row, _plan(lib, h, row), golden[row["id"]])
+                plan = _plan(lib, h, row)
+                # every template argument of every stage, as recorded on the GPU
+                assert plan["names"] == golden[row["id"]], (row["id"], plan)
+                _check_plan_against_names(row, plan, golden[row["id"]])
         finally:
             lib.qd_graph_destroy(h)
 
 
 def test_plan_matches_recorded_dispatch():
-    """The pure planner (qd_graph_plan on host-only graphs, no GPU) against what
-    the launch layer actually launched before the plan existed
-    (tests/golden/dispatch_names.json, recorded on an MI355X by
-    tools/record_dispatch.py): BP and SSF kernel families, pre-pass or not, and
-    which packed decodes the triage reads directly; the wave graph and the two
-    workgroup graphs."""
+    """The pure planner (qd_graph_plan and qd_graph_plan_names on host-only
+    graphs, no GPU) against what the launch layer actually launched before the
+    plan existed (tests/golden/dispatch_names.json, recorded on an MI355X by
+    tools/record_dispatch.py): the exact instantiation of every stage (all three
+    names, every template argument), BP and SSF kernel families, pre-pass or
+    not, and which packed decodes the triage reads directly; the wave graph and
+    the two workgroup graphs."""
     from tools import record_dispatch as rd
     _check_plans_of([rd.WAVE_GRAPH] + rd.BLOCK_GRAPHS)
 
@@ -621,6 +639,57 @@ def test_plan_expands_packed_rows_the_triage_cannot_step():
                                              _abi.ptr(out)), "qd_graph_plan")
                 assert out[0] == 2 and out[2] == 1, (m, n, out)  # the two-pass path either way
                 assert bool(out[3]) == (not direct), (m, n, out)
+        finally:
+            lib.qd_graph_destroy(h)
+
+
+def test_plan_names_every_wave_shape():
+    """Every wave shape has an instantiation for every decode the plan can ask
+    of it: one random graph per entry of QDEC_WAVE_SHAPES, method x precision x
+    {lean, x} x packed x occupancy {0, 12}.  The plan succeeds; the BP name is
+    of the planned family and carries the graph's shape (which the pads
+    confirm); OCC = 3 is planned only for double at occupancy 12; the triage's
+    PK is true exactly when the plan leaves packed rows unexpanded."""
+    import ctypes as C
+    import itertools
+    import re
+
+    from exp_ldpc_amd import _abi
+    from test_gpu_compact import WAVE_SHAPE_GRAPHS, wave_shape_graph
+    lib = _abi.load()
+    for (rc, rv, drc) in WAVE_SHAPE_GRAPHS:
+        H, probs, lz = wave_shape_graph((rc, rv, drc))
+        h, _, _ = _host_graph(lib, H, lz=lz, probs=probs)
+        try:
+            m_pad, n_pad = C.c_int32(0), C.c_int32(0)
+            _abi.check(lib.qd_graph_ms_state0_copy(h, _abi.QD_F64, None, None, C.byref(m_pad)), "state0")
+            _abi.check(lib.qd_graph_it1_tables_copy(h, _abi.QD_F64, None, None, C.byref(n_pad)), "it1 tables")
+            assert (m_pad.value, n_pad.value) == (64 * rc, 64 * rv), (rc, rv, drc)
+            for method, precision, out, packed, occ in itertools.product(
+                    ("ms", "ps"), ("f32", "f64"), ("lean", "x"), (False, True), (0, 12)):
+                row = {"id": f"{rc}-{rv}-{drc}-{method}-{precision}-{out}-{packed}-{occ}", "method": method,
+                       "precision": precision, "out": out, "ssf": False, "packed": packed, "options": {}, "occ": occ,
+                       "misaligned": False}
+                plan = _plan(lib, h, row, B=65)
+                bp, ssf, pre = plan["names"]
+                family = PLAN_BP[plan["bp"]]
+                tname = {"f32": "float", "f64": "double"}[precision]
+                args = re.fullmatch(re.escape(family) + "<(.*)>", bp)
+                assert args, (row["id"], plan)
+                args = args.group(1).split(", ")
+                assert args[0] == tname and plan["bp"] == (0 if method == "ps" else 2 if out == "lean" else 1), \
+                    (row["id"], plan)
+                shape_at = 2 if plan["bp"] == 0 else 1  # bp_wave_kernel: <T, METHOD, RC, RV, DRC, ...>
+                assert args[shape_at:shape_at + 3] == [str(rc), str(rv), str(drc)], (row["id"], plan)
+                # OCC: the one-pass kernel's last argument, the compact kernel's last but one
+                occ_arg = {0: "0", 1: args[-1], 2: args[-2]}[plan["bp"]]
+                assert occ_arg in ("0", "3") and (occ_arg != "3" or (precision == "f64" and occ == 12)), \
+                    (row["id"], plan)
+                assert ssf == "" and bool(pre) == bool(plan["two_pass"]), (row["id"], plan)
+                if pre:
+                    assert pre == f"qdec::ms_triage_kernel<{rc}, {rv}, " \
+                                  f"{'true' if packed and not plan['expand_packed'] else 'false'}>", (row["id"], plan)
+                assert bool(plan["expand_packed"]) == (packed and not pre.endswith("true>")), (row["id"], plan)
         finally:
             lib.qd_graph_destroy(h)
 

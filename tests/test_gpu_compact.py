@@ -40,6 +40,60 @@ def _random_graph(rng, m, n, dmax=7, cmax=4):
     return make_check_matrix(rows, n)
 
 
+# one random graph per entry of QDEC_WAVE_SHAPES (qdec_graph.h): (RC, RV, DRC) ->
+# (m, n, largest row degree drawn), sized so that pick_wave_shape returns that
+# entry (the first shape with 64 RC >= m, 64 RV >= n and DRC >= the row degree);
+# odd m and n, no multiple of the 64-lane rounds
+WAVE_SHAPE_GRAPHS = {(1, 2, 8): (40, 90, 7), (2, 3, 6): (110, 170, 6), (2, 3, 8): (110, 170, 8),
+                     (2, 4, 7): (120, 230, 7), (2, 4, 8): (120, 230, 8), (2, 6, 8): (100, 370, 7),
+                     (4, 9, 8): (200, 520, 7)}
+
+
+def wave_shape_graph(shape):
+    """(H, priors, logicals) of the shape's graph: ragged rows, random priors, k = 3."""
+    m, n, dmax = WAVE_SHAPE_GRAPHS[shape]
+    rng = np.random.default_rng(m * 1000 + n + dmax)
+    H = _random_graph(rng, m, n, dmax=dmax)
+    return H, rng.uniform(0.005, 0.05, n), (rng.random((3, n)) < 0.05).astype(np.uint8)
+
+
+@pytest.mark.parametrize("shape", list(WAVE_SHAPE_GRAPHS))
+def test_last_kernels_equal_the_plan(gpu_available, oracle_lib, shape):
+    """What a decode launched is what the plan named: on every wave shape, B =
+    65 (one full 64-shot triage tile plus one shot), min-sum f64 and f32 lean
+    with the fused logical check and product-sum f32 writing x, last_kernels()
+    equals qd_graph_plan_names for the same call, and every output equals the
+    oracle's."""
+    import torch
+
+    from exp_ldpc_amd.decoder import Decoder
+    H, probs, L = wave_shape_graph(shape)
+    m, n = H.shape
+    B = 65
+    rng = np.random.default_rng(m + n)
+    e = (rng.random((B, n)) < 0.02).astype(np.uint8)
+    e[: B // 3] = 0
+    syn = np.ascontiguousarray(((H @ e.T).T % 2).astype(np.uint8))
+    rd = (e ^ (rng.random((B, n)) < 0.01)).astype(np.uint8)
+    dev = torch.device("cuda", 0)
+    for method, precision, keys in (("ms", "f64", ()), ("ms", "f32", ()), ("ps", "f32", ("x",))):
+        dec = Decoder(H, probs, method=method, precision=precision, max_iter=20, logicals=L)
+        out = {k: torch.full((B,), 77, dtype=getattr(torch, dt), device=dev) for k, dt in OUTS if k != "ssf_steps"}
+        if "x" in keys:
+            out["x"] = torch.full((B, n), 77, dtype=torch.uint8, device=dev)
+        dec.decode_device(B, syn=torch.from_numpy(syn).to(dev), readout=torch.from_numpy(rd).to(dev), **out)
+        torch.cuda.synchronize()
+        names = dec.last_kernels()
+        assert names == dec.planned_kernels(B, present=("syn", "readout", "fail") + keys), (method, precision)
+        family = "qdec::bp_ms_cmp_kernel" if method == "ms" else "qdec::bp_wave_kernel"
+        assert names[0].startswith(family + "<") and ", ".join(map(str, shape)) in names[0], names
+        assert bool(names[2]) == (method == "ms") and names[1] == "", names
+        ref = oracle_lib.decode(H, probs, syn, method=method, precision=precision, max_iter=20, lz=L, readout=rd,
+                                want_llr=False)
+        for key, v in out.items():
+            assert np.array_equal(v.cpu().numpy(), ref[key]), (method, precision, key)
+
+
 @pytest.mark.parametrize("precision", ["f32", "f64"])
 @pytest.mark.parametrize("mn", [(40, 90), (110, 170), (120, 230), (100, 370), (200, 520)])
 def test_compact_every_wave_shape(gpu_available, oracle_lib, precision, mn, monkeypatch):
