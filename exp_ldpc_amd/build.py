@@ -19,8 +19,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libqdec_hip.so")
-SOURCES = ["qdec_abi.cpp", "qdec_tables.cpp", "qdec_osd.cpp", "qdec_gf2.cpp", "qdec_hgp.cpp", "qdec_bp.hip", "qdec_bp_block.hip",
-           "qdec_sample.hip", "qdec_osd.hip"]
+# longest-compiling first, so the pool starts the big units first (DESIGN §3.0 has the times)
+SOURCES = ["qdec_osd.hip", "qdec_ms_rvx.hip", "qdec_bp.hip", "qdec_ms_rv4.hip", "qdec_bp_block.hip",
+           "qdec_bp_group.hip", "qdec_ms_triage.hip", "qdec_ms_lds64.hip", "qdec_ms_lds.hip", "qdec_tables.cpp",
+           "qdec_launch_wave.hip", "qdec_launch_block.hip", "qdec_abi.cpp", "qdec_osd.cpp", "qdec_hgp.cpp",
+           "qdec_sample.hip", "qdec_gf2.cpp"]
 # device source compiled at run time (hipRTC, per hypergraph-product code): embedded
 # into the library as a string literal (build/gen/qdec_hgp_src.inc)
 RTC_SOURCES = ["qdec_hgp_kernel.hip"]

@@ -1,6 +1,10 @@
-// qdec_bp.hip -- BP + small-set-flip syndrome decoding on gfx950.
+// qdec_bp.hip -- wave graphs: the message-array BP kernel (built for
+// product-sum) and the small-set-flip kernels, with their table builders.  The
+// plan and the launchers are qdec_launch_wave.hip; the min-sum BP kernels are
+// qdec_bp_ms.h (units qdec_ms_rv4.hip, qdec_ms_rvx.hip), the triage
+// qdec_ms_triage.hip.
 //
-// Two kernels per decode call:
+// A product-sum decode with SSF runs two of this unit's kernels:
 //
 // 1. bp_wave_kernel: one wave64 decodes one shot at a time (workgroup = one
 //    wave; persistent grid walking the shot range).  Everything a shot touches
@@ -17,9 +21,10 @@
 //    slot table held in registers; the variable pass does the mirror image.
 //    With SSF requested, shots BP did not converge on are appended (hard
 //    decision + residual syndrome) to an HBM work queue instead of finalised.
-// 2. ssf_wave_kernel: one wave per queued shot runs small-set-flip and
-//    finalises it.  Only failing shots are touched (compacted), and the BP
-//    kernel's register budget does not carry the SSF scan.
+// 2. ssf_wave_kernel (or the table-driven ssf_lut_kernel): one wave per queued
+//    shot runs small-set-flip and finalises it.  Only failing shots are touched
+//    (compacted), and the BP kernel's register budget does not carry the SSF
+//    scan.  The min-sum BP kernels feed the same queue.
 //
 // Arithmetic is the ldpc v1 bp_decoder restated (oracle/bp_impl.inc is the CPU
 // copy of the same loops): min-sum in the log domain with alpha_t = 1 - 2^-t
@@ -39,7 +44,7 @@
 #include <cstdlib>
 
 #include "qdec_device.h"
-#include "qdec_bp_ms.h"
+#include "qdec_shot_seq.h"
 #include "qdec_kernels.h"
 
 namespace qdec {
@@ -875,12 +880,14 @@ __global__ __launch_bounds__(64 * kLutWaves, LEAN ? kLutOcc : 4) void ssf_lut_ke
     }
 }
 
-// ---------------------------------------------------------------- launcher
-LaunchNames& last_launch_names() {
-    static thread_local LaunchNames n;
-    return n;
-}
+QDEC_STAMPS_READER(read_stamps_bp)
 
+// ---------------------------------------------------------------- kernel tables
+// The launch plan and the launchers are qdec_launch_wave.hip; this unit exports
+// its families' table builders (qdec_kernels.h).  bp_wave_kernel and the SSF
+// kernels stay one unit because they share finalize_shot: compiled without the
+// SSF kernels, all 28 bp_wave_kernel instantiations come out with other code
+// sizes and SGPR spill counts.
 template <typename T>
 static size_t wave_lds_bytes(const DevGraph& g) {
     constexpr int DRS = lds_stride<T, kDR>();
@@ -889,434 +896,46 @@ static size_t wave_lds_bytes(const DevGraph& g) {
            (size_t)g.n_pad + 64;
 }
 
-// ---------------------------------------------------------------- kernel tables
-// Every instantiation of the wave-graph families this unit builds, one table
-// per family; entries are found by their template arguments (find_kernel).
-// Argument order of the entries' t[]:
-//   bp_wave_kernel    T, METHOD, RC, RV, DRC, DEFER
-//   bp_ms_wave_kernel T, RC, RV, DRC, DEFER, LEAN, D3R, OCC
-//   bp_ms_cmp_kernel  T, RC, RV, DRC, DEFER, D3R, OCC, FUSE
-//   ms_triage_kernel  RC, RV, PK
-//   ssf_wave_kernel   RG, XW, RW
-//   ssf_lut_kernel    RG, XW, RW, LEAN
-struct WaveTables {
-    KernelTable bp_wave, ms_wave, ms_cmp, triage, ssf_wave, ssf_lut;
-};
-
-// The rules that restrict the set (the tables are built by them, the plan picks
-// by them).  Every shape of QDEC_WAVE_SHAPES has every family; bp_wave_kernel
-// is built for product-sum only (min-sum has its own kernels).
-// D3R = 2 (two leading variable rounds of degree <= 3): only on shape (2, 4, 7),
-// the n = 225 HGP code with its 144 degree-3 columns
-constexpr bool wave_has_d3r2(int rc, int rv, int drc) { return rc == 2 && rv == 4 && drc == 7; }
-// OCC = 3 (three waves per SIMD): only for double with D3R = 2, and for the
-// one-pass kernel only with LEAN (the 168-VGPR build)
-constexpr bool wave_has_occ3(int precision, int d3r) { return precision == 0 && d3r == 2; }
-// FUSE (the table-driven SSF inside the compact kernel) only with DEFER
-
-template <typename T, int RC, int RV, int DRC, bool DEFER, bool LEAN, int D3R, int OCC>
-static void add_ms_wave(KernelTable& t) {
-    t.push_back(QDEC_INST(64, bp_ms_wave_kernel, T, RC, RV, DRC, DEFER, LEAN, D3R, OCC));
-    t.back().lds = [](const DevGraph& g, const DecodeArgs&) { return MsLds<T>::template bytes<RC, RV>(g); };
-}
-
-template <typename T, int RC, int RV, int DRC, bool DEFER, int D3R, int OCC, int FUSE>
-static void add_ms_cmp(KernelTable& t) {
-    static_assert(DEFER || FUSE == 0, "FUSE only with DEFER");
-    t.push_back(QDEC_INST(64, bp_ms_cmp_kernel, T, RC, RV, DRC, DEFER, D3R, OCC, FUSE));
-    t.back().lds = [](const DevGraph& g, const DecodeArgs&) {
-        size_t b = MsLds<T>::core_bytes(g) + ((size_t)g.k * RV * 8 + 15) / 16 * 16 + 2 * kCmpLists * kCmpSegs * 8;
-        if (FUSE) b += ((size_t)RV * 8 + (size_t)g.m_pad * 2 + 15) / 16 * 16;  // fused SSF: xb, flog
-        return b;
-    };
-}
-
-template <typename T, int RC, int RV, int DRC, bool DEFER, int D3R, int OCC>
-static void add_ms_occ(WaveTables& t) {
-    if constexpr (OCC == 0) add_ms_wave<T, RC, RV, DRC, DEFER, false, D3R, OCC>(t.ms_wave);
-    add_ms_wave<T, RC, RV, DRC, DEFER, true, D3R, OCC>(t.ms_wave);
-    add_ms_cmp<T, RC, RV, DRC, DEFER, D3R, OCC, 0>(t.ms_cmp);
-    if constexpr (DEFER) {
-        add_ms_cmp<T, RC, RV, DRC, DEFER, D3R, OCC, 1>(t.ms_cmp);
-        add_ms_cmp<T, RC, RV, DRC, DEFER, D3R, OCC, 2>(t.ms_cmp);
-    }
-}
-
 template <typename T, int RC, int RV, int DRC, bool DEFER>
-static void add_bp_defer(WaveTables& t) {
-    t.bp_wave.push_back(QDEC_INST(64, bp_wave_kernel, T, 0, RC, RV, DRC, DEFER));
-    t.bp_wave.back().lds = [](const DevGraph& g, const DecodeArgs&) { return (wave_lds_bytes<T>(g) + 15) / 16 * 16; };
-    add_ms_occ<T, RC, RV, DRC, DEFER, 0, 0>(t);
-    if constexpr (wave_has_d3r2(RC, RV, DRC)) {
-        add_ms_occ<T, RC, RV, DRC, DEFER, 2, 0>(t);
-        if constexpr (wave_has_occ3(sizeof(T) == 4 ? 1 : 0, 2)) add_ms_occ<T, RC, RV, DRC, DEFER, 2, 3>(t);
-    }
+static void add_bp_wave(KernelTable& t) {
+    t.push_back(QDEC_INST(64, bp_wave_kernel, T, 0, RC, RV, DRC, DEFER));
+    t.back().lds = [](const DevGraph& g, const DecodeArgs&) { return (wave_lds_bytes<T>(g) + 15) / 16 * 16; };
 }
 
-template <int RC, int RV, bool PK>
-static void add_triage(KernelTable& t) {
-    t.push_back(QDEC_INST(64, ms_triage_kernel, RC, RV, PK));
-    // the logicals, the tile images (byte rows), the iteration-1 words (over
-    // the images; the kernel's layout, ms_triage_kernel)
-    t.back().lds = [](const DevGraph& g, const DecodeArgs& a) {
-        const bool want_fail = a.fail && a.readout && g.k > 0;
-        const size_t tiles = PK ? 0 : triage_img_bytes(64 * (int64_t)g.m) + triage_img_bytes(64 * (int64_t)g.n_data);
-        const size_t it1 = a.it1_lut ? TriageIt1<RC, RV>::bytes : 0;
-        return ((want_fail ? (size_t)g.k * g.lz_words * 8 : 0) + 15) / 16 * 16 + tiles + it1;
-    };
-}
-
-// the families that depend on the rounds only: the shapes share them ((2, 3, *), (2, 4, *))
-template <int RG, int RC, int RV>
-static void add_ssf(WaveTables& t) {
-    t.ssf_wave.push_back(QDEC_INST(64 * kSsfWaves, ssf_wave_kernel, RG, RV, RC));
-    t.ssf_wave.back().lds = [](const DevGraph& g, const DecodeArgs&) {
-        return SsfLds<RG>::shared_bytes(g) + kSsfWaves * SsfLds<RG>::wave_bytes(g);
-    };
-    t.ssf_lut.push_back(QDEC_INST(64 * kLutWaves, ssf_lut_kernel, RG, RV, RC, false));
-    t.ssf_lut.push_back(QDEC_INST(64 * kLutWaves, ssf_lut_kernel, RG, RV, RC, true));
-}
-
-template <int RC, int RV, int DRC>
-static void add_wave_shape(WaveTables& t) {
-    add_bp_defer<float, RC, RV, DRC, false>(t);
-    add_bp_defer<float, RC, RV, DRC, true>(t);
-    add_bp_defer<double, RC, RV, DRC, false>(t);
-    add_bp_defer<double, RC, RV, DRC, true>(t);
-    if (find_kernel(t.triage, {RC, RV, 0})) return;
-    add_triage<RC, RV, false>(t.triage);
-    add_triage<RC, RV, true>(t.triage);
-    add_ssf<1, RC, RV>(t);
-    add_ssf<2, RC, RV>(t);
-}
-
-static const WaveTables& wave_tables() {
-    static const WaveTables tables = [] {
-        WaveTables t;
-#define QDEC_SHAPE(R, V, D) add_wave_shape<R, V, D>(t);
-        QDEC_WAVE_SHAPES(QDEC_SHAPE)
-#undef QDEC_SHAPE
-        return t;
-    }();
-    return tables;
-}
-
-// ---------------------------------------------------------------- launch plan
-// Wave graphs.  Lean launches: no x / corr / llr outputs, no base, no syndrome
-// flags, no fold (and, with SSF, the packed queue).  The two-pass path
-// (ms_triage_kernel + bp_ms_cmp_kernel) serves lean min-sum launches whose graph
-// has the slot-order logicals (or no fused check) and whose rows the triage can
-// load: 16-B aligned byte rows, 8-B aligned packed rows.  QD_OPT_COMPACT = 0
-// keeps the one-pass kernel (A/B, parity tests run both).
-static void plan_decode_wave(const DevGraph& g, const DecodeArgs& a, DecodePlan& p) {
-    // the wave SSF kernels read the packed queue (register-owned generators, u8 local-check ids)
-    const bool ssf_wave = g.n_gen <= 128 && g.g_lc8;
-    p.placement = 3;
-    p.q_packed = a.ssf && ssf_wave ? 1 : 0;
-    const bool plain = !a.x_out && !a.corr_out && !a.llr_out && !a.base && !a.syn_flags && g.fold_blocks == 1;
-    p.lean = plain && (!a.ssf || p.q_packed);
-    const uintptr_t al = a.in_packed ? 7 : 15;
-    const bool aligned = !(reinterpret_cast<uintptr_t>(a.syn) & al) &&
-                         !(a.readout && (reinterpret_cast<uintptr_t>(a.readout) & al));
-    const bool want_fail = a.fail && a.readout && g.k > 0;
-    // g.ms_vslot: the slot tables the compact kernel reads are built.  With SSF
-    // the queue entries carry readout parities, whose area holds n_pad / 64
-    // words: up to n_pad logicals
-    p.two_pass = p.method == 1 && g.ms_vslot && g.opt_compact && a.syn && aligned && p.lean &&
-                 (!want_fail || g.ms_lzs) && (!a.ssf || g.k <= g.n_pad);
-    p.q_rpar = p.two_pass && a.ssf ? 1 : 0;
-    p.bp = p.method != 1 ? kBpWave : p.two_pass ? kBpTwoPass : kBpMsWave;
-    // packed rows: the triage steps through m_pad / 64 words per syndrome row,
-    // the rows hold ceil(m / 64); every other reader wants byte rows
-    p.expand_packed = a.in_packed && !(p.two_pass && g.m_pad / 64 == (g.m + 63) / 64);
-    const bool lut = g.s_lut && g.s_tog && g.opt_ssf == kSsfAuto;
-    if (!a.ssf) {
-        p.ssf = kFinNone;
-    } else if (p.q_rpar && g.opt_ssf_fuse && lut) {
-        // the compact BP kernel runs the table-driven SSF itself (QD_OPT_SSF_FUSE;
-        // same tables and spec as ssf_lut_kernel)
-        p.ssf = kFinFused;
-        p.fuse = g.n_gen <= 64 ? 1 : 2;
-    } else if (!ssf_wave) {
-        p.ssf = ssf_fin_path(g, a);
-    } else if (lut) {
-        p.ssf = kFinLut;
-        p.ssf_lean = !a.x_out && !a.corr_out && !a.base && g.fold_blocks == 1;
-    } else {
-        p.ssf = g.opt_ssf == kSsfScanGather    ? kFinScanGather
-                : g.opt_ssf == kSsfScanNoSplit ? kFinScanNoSplit
-                                               : kFinScan;
-    }
-
-    // ---- the instantiation of every stage ----
-    const WaveTables& t = wave_tables();
-    const int rc = g.m_pad / 64, rv = g.n_pad / 64, drc = g.shape_drc;
-    const int defer = p.ssf != kFinNone;  // the BP kernels' DEFER (the fused SSF is compiled under it too)
-    if (p.method == 1) {
-        // f64: 2 waves per SIMD measured faster than 3 for a lone decode at every
-        // p (n = 225: 7.1 vs 9.3 ms per 2^18 shots at p = 0.1); concurrent
-        // decodes may ask for more (qd_graph_set_wave_occupancy)
-        p.wave_cap = g.wave_occ > 0 ? g.wave_occ : (p.precision == 0 ? 8 : 0);
-        const int d3r = wave_has_d3r2(rc, rv, drc) && g.ms_d3r >= 2 ? 2 : 0;
-        const bool occ3 = wave_has_occ3(p.precision, d3r) && p.wave_cap > 8;  // 3 waves per SIMD
-        if (p.two_pass) {
-            p.pre_k = find_kernel(t.triage, {rc, rv, a.in_packed && !p.expand_packed});
-            p.bp_k = find_kernel(t.ms_cmp, {p.precision, rc, rv, drc, defer, d3r, occ3 ? 3 : 0, p.fuse});
-            if (!p.pre_k) p.missing = "ms_triage_kernel";
-        } else {
-            p.bp_k = find_kernel(t.ms_wave, {p.precision, rc, rv, drc, defer, p.lean, d3r, occ3 && p.lean ? 3 : 0});
-        }
-    } else {
-        p.bp_k = find_kernel(t.bp_wave, {p.precision, 0, rc, rv, drc, defer});
-    }
-    if (!p.bp_k) p.missing = "wave BP kernel";
-    const int rg = g.n_gen <= 64 ? 1 : 2;
-    if (p.ssf == kFinLut) p.fin_k = find_kernel(t.ssf_lut, {rg, rv, rc, p.ssf_lean});
-    else if (p.ssf == kFinScan || p.ssf == kFinScanGather || p.ssf == kFinScanNoSplit)
-        p.fin_k = find_kernel(t.ssf_wave, {rg, rv, rc});
-    else if (p.ssf != kFinNone && p.ssf != kFinFused) p.fin_k = ssf_block_entry(p.ssf);
-    if (p.ssf != kFinNone && p.ssf != kFinFused && !p.fin_k) p.missing = "wave SSF kernel";
-}
-
-DecodePlan plan_decode(const DevGraph& g, int method, int precision, const DecodeArgs& a) {
-    DecodePlan p{};
-    p.method = method;
-    p.precision = precision;
-    if (g.wave && wave_kernel_supports(g)) plan_decode_wave(g, a, p);
-    else plan_decode_block(g, a, p);
-    p.defer = p.ssf != kFinNone && p.ssf != kFinFused;
-    p.need_queue = p.ssf != kFinNone;
-    p.need_lists = p.two_pass;
-    p.need_unpack = p.expand_packed;
-    return p;
-}
-
-static int launch_triage(const DevGraph& g, const KernelEntry& k, const DecodeArgs& a, hipStream_t stream) {
-    const bool want_fail = a.fail && a.readout && g.k > 0;
-    // the tile loads are 16-B vector loads (packed rows: u64 loads); the list
-    // counters take u64 atomics on their own 128-B lines, entries 16-B stores
-    const uintptr_t al = a.in_packed ? 7 : 15;
-    if ((reinterpret_cast<uintptr_t>(a.syn) & al) || (want_fail && (reinterpret_cast<uintptr_t>(a.readout) & al)))
-        return (int)hipErrorInvalidValue;
-    if (!a.cmp || !a.cmp_count || (reinterpret_cast<uintptr_t>(a.cmp_count) & 127) ||
-        (reinterpret_cast<uintptr_t>(a.cmp) & 15))
-        return (int)hipErrorInvalidValue;
-    if (a.it1_lut && (!g.it1_vchk || !g.it1_cvar || g.m_pad != 64 * k.t[0] || g.n_pad != 64 * k.t[1]))
-        return (int)hipErrorInvalidValue;
-    const size_t lds = k.lds(g, a);
-    if (lds > 64 * 1024) {  // large logical tables (k <= 256, lz_words <= 9)
-        const hipError_t ea = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return (int)ea;
-    }
-    last_launch_names().pre = noted_name(&k);
-    return launch_entry(WaveSig{}, k, (a.B + 63) / 64, lds, stream, g, a);
-}
-
-// one-wave BP blocks, each taking shots (or list chunks) until none are left
-static int launch_persistent(const KernelEntry& k, size_t lds, int num_cus, hipStream_t stream, const DevGraph& g,
-                             const DecodeArgs& a, int max_per_cu = 0) {
-    last_launch_names().bp = noted_name(&k);
-    return launch_entry_resident(WaveSig{}, k, lds, num_cus, a.B, stream, GridRule{max_per_cu, true}, g, a);
-}
-
-// The plan's BP stage on a wave graph: min-sum uses the compressed-state
-// kernels, product-sum the message-array kernel.
-static int launch_bp_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
-                          hipStream_t stream, bool* triaged) {
-    if (p.bp == kBpWave) return launch_persistent(*p.bp_k, p.bp_k->lds(g, a), num_cus, stream, g, a);
-    // the fused failure check reads the dense logical table's LDS copy
-    // (lz_in_lds); wave-kernel graphs always have one (n <= 576)
-    if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
-    if (a.wave_ctr && !p.two_pass) {  // ShotSeq's chunk counter (two passes: the triage zeroes it)
-        const hipError_t e = hipMemsetAsync(a.wave_ctr, 0, sizeof(unsigned long long), stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    const int cap = p.wave_cap;
-    if (!p.two_pass) return launch_persistent(*p.bp_k, p.bp_k->lds(g, a), num_cus, stream, g, a, cap);
-    // triage, then the listed shots
-    // the compact kernel starts every listed shot from the first check state
-    if (!g.ms_state0[p.precision]) return (int)hipErrorInvalidValue;
-    DecodeArgs b = a;
-    b.cmp_zero_ok = (g.ms_allpos >> p.precision) & 1;
-    // iteration 1 in the triage: the tables assume alpha_1 = 0.5 (the
-    // default schedule); QD_OPT_TRIAGE_IT1 = 0 leaves it to the BP kernel
-    b.it1_lut = (a.ms_scaling == 0.0 && a.max_iter >= 1 && g.opt_triage_it1) ? g.it1_lut[p.precision] : nullptr;
-    if (!b.cmp_count_next) {  // double-buffered counters arrive zeroed (the previous triage)
-        const hipError_t e = hipMemsetAsync(b.cmp_count, 0, (size_t)kCmpLists * kCmpSegs * 128, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    const int rc = launch_triage(g, *p.pre_k, b, stream);
-    if (rc != 0) return rc;
-    *triaged = true;
-    if (b.ev) (void)hipEventRecord(b.ev[3], stream);  // end of the pre-pass
-    size_t clds = p.bp_k->lds(g, b);
-    // a capped grid (f64: 8 waves per CU) must also be placed evenly: the
-    // dispatcher stacks up to the kernel's own occupancy on a CU (11 for
-    // the 159-VGPR f64 kernel) while others sit idle, so the LDS request is
-    // padded to 1/cap of the CU
-    if (cap > 0) clds = std::max(clds, (size_t)(160 * 1024 / cap) / 16 * 16);
-    return launch_persistent(*p.bp_k, clds, num_cus, stream, g, b, cap);
-}
-
-static int launch_ssf_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus,
-                           hipStream_t stream) {
-    // the fused failure check reads the dense logical table's LDS copy (as launch_bp_wave)
-    if (a.fail && g.k > 0 && !g.lz) return (int)hipErrorInvalidValue;
-    const KernelEntry& k = *p.fin_k;
-    const bool lut = p.ssf == kFinLut;
-    const int waves = lut ? kLutWaves : kSsfWaves;
-    const size_t lds = lut ? SsfLutLds::shared_bytes(g) + kLutWaves * SsfLutLds::wave_bytes(g) : k.lds(g, a);
-    if (lut && lds > 160 * 1024) return (int)hipErrorInvalidConfiguration;
-    last_launch_names().ssf = noted_name(&k);
-    return launch_entry_resident(WaveSig{}, k, lds, num_cus, (a.B + waves - 1) / waves /* queue length <= B */, stream,
-                                 {}, g, a);
-}
-
-static int launch_wave(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a0, int num_cus, hipStream_t stream,
-                       bool* triaged) {
-    DecodeArgs a = a0;
-    a.q_packed = p.q_packed;
-    a.q_w = reinterpret_cast<uint64_t*>(a.q_x);
-    a.q_rpar = p.q_rpar;
-    if (p.ssf != kFinNone && (!a.q_count || !a.q_idx || !a.q_x || !a.q_r)) return (int)hipErrorInvalidValue;
-    if (p.ssf == kFinNone || p.ssf == kFinFused) {  // the BP kernel finishes every shot
-        record_ev(a, 0, stream);
-        const int rc = launch_bp_wave(g, p, a, num_cus, stream, triaged);
-        record_ev(a, 1, stream);
-        record_ev(a, 2, stream);
-        return rc;
-    }
-    if (!a.q_rpar) {  // the compact path's triage zeroes both counters itself (one launch fewer each)
-        hipError_t e = hipMemsetAsync(a.q_count, 0, sizeof(int32_t), stream);
-        if (e == hipSuccess && a.wave_ctr)  // the SSF kernel's slot counter (ShotSeq)
-            e = hipMemsetAsync(a.wave_ctr + 1, 0, sizeof(unsigned long long), stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    record_ev(a, 0, stream);
-    int rc = launch_bp_wave(g, p, a, num_cus, stream, triaged);
-    record_ev(a, 1, stream);
-    if (rc != 0) return rc;
-    if (p.ssf == kFinIncBlock || p.ssf == kFinBlockLds) {  // generators the wave SSF kernels do not hold
-        rc = launch_ssf_block(g, p, a, num_cus, stream);
-        record_ev(a, 2, stream);
-        return rc;
-    }
-    hipStream_t ss = stream;
-    if (a.ssf_stream && a.ssf_stream != stream && a.ssf_ev) {  // SSF behind an event on its own stream
-        hipError_t e2 = hipEventRecord(a.ssf_ev, stream);
-        if (e2 == hipSuccess) e2 = hipStreamWaitEvent(a.ssf_stream, a.ssf_ev, 0);
-        if (e2 != hipSuccess) return (int)e2;
-        ss = a.ssf_stream;
-    }
-    DevGraph gs = g;  // QD_SSF_SCAN_GATHER: no incremental local syndromes
-    if (p.ssf == kFinScanGather) gs.g_inv = nullptr;
-    rc = launch_ssf_wave(gs, p, a, num_cus, ss);
-    record_ev(a, 2, ss);
-    return rc;
-}
-
-bool wave_kernel_supports(const DevGraph& g) {
-    bool shape = false;
-#define QDEC_SHAPE(R, V, D) shape |= (g.m_pad == 64 * R && g.n_pad == 64 * V && g.shape_drc == D);
+void add_bp_wave_kernels(KernelTable& t) {
+#define QDEC_SHAPE(R, V, D)                 \
+    add_bp_wave<float, R, V, D, false>(t);  \
+    add_bp_wave<float, R, V, D, true>(t);   \
+    add_bp_wave<double, R, V, D, false>(t); \
+    add_bp_wave<double, R, V, D, true>(t);
     QDEC_WAVE_SHAPES(QDEC_SHAPE)
 #undef QDEC_SHAPE
-    return shape && g.max_rdeg <= kDR && g.max_cdeg <= kDC && g.k <= 256;
 }
 
-// ---------------------------------------------------------------- packed inputs
-// Bit-packed rows (QD_INPUT_PACKED) expanded to one byte per bit: dst[r][c] =
-// bit c of src row r (words of `words` u64 per row).  Grid-stride over 4-byte
-// groups of the output (coalesced stores; the source words are re-read from
-// L1/L2 by neighbouring threads).
-__global__ void unpack_rows_kernel(const uint64_t* __restrict__ src, int64_t rows, int cols, int words,
-                                   uint8_t* __restrict__ dst) {
-    const int64_t total = rows * cols;
-    for (int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; e < total;
-         e += (int64_t)gridDim.x * blockDim.x * 4) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int64_t q = e + t;
-            if (q < total) {
-                const int64_t r = q / cols;
-                const int c = (int)(q - r * cols);
-                dst[q] = (uint8_t)((src[r * words + (c >> 6)] >> (c & 63)) & 1ull);
-            }
-        }
+// the SSF kernels depend on the rounds only: the shapes share them ((2, 3, *), (2, 4, *))
+template <int RG, int RC, int RV>
+static void add_ssf(KernelTable& scan, KernelTable& lut) {
+    scan.push_back(QDEC_INST(64 * kSsfWaves, ssf_wave_kernel, RG, RV, RC));
+    scan.back().lds = [](const DevGraph& g, const DecodeArgs&) {
+        return SsfLds<RG>::shared_bytes(g) + kSsfWaves * SsfLds<RG>::wave_bytes(g);
+    };
+    for (bool lean : {false, true}) {
+        lut.push_back(lean ? QDEC_INST(64 * kLutWaves, ssf_lut_kernel, RG, RV, RC, true)
+                           : QDEC_INST(64 * kLutWaves, ssf_lut_kernel, RG, RV, RC, false));
+        lut.back().lds = [](const DevGraph& g, const DecodeArgs&) {
+            return SsfLutLds::shared_bytes(g) + kLutWaves * SsfLutLds::wave_bytes(g);
+        };
     }
 }
 
-static int launch_unpack_rows(const uint8_t* src, int64_t rows, int cols, uint8_t* dst, int num_cus,
-                              hipStream_t stream) {
-    if (rows <= 0 || cols <= 0) return 0;
-    const int64_t groups = (rows * cols + 3) / 4;
-    const long long blocks = std::min<long long>((groups + 255) / 256, (long long)num_cus * 16);
-    hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
-                       reinterpret_cast<const uint64_t*>(src), rows, cols, (cols + 63) / 64, dst);
-    return (int)hipGetLastError();
-}
-
-int launch_decode(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a0, int num_cus, hipStream_t stream,
-                  void* scratch, size_t scratch_bytes, bool* triaged) {
-    last_launch_names() = LaunchNames{};
-    *triaged = false;
-    if (a0.B <= 0) return 0;
-    DecodeArgs a = a0;
-    if (p.expand_packed) {
-        // byte rows for every reader but the triage's packed branch
-        if (!a.unpack_buf) return (int)hipErrorInvalidValue;
-        uint8_t* u = a.unpack_buf;
-        int rc = 0;
-        if (a.syn) {
-            rc = launch_unpack_rows(a.syn, a.B, g.m, u, num_cus, stream);
-            a.syn = u;
-            u += unpack_region(a.B, g.m);
-        }
-        if (rc == 0 && a.base) {
-            rc = launch_unpack_rows(a.base, a.B, g.n_data, u, num_cus, stream);
-            a.base = u;
-            u += unpack_region(a.B, g.n_data);
-        }
-        if (rc == 0 && a.readout) {
-            rc = launch_unpack_rows(a.readout, a.B, g.n_data, u, num_cus, stream);
-            a.readout = u;
-        }
-        if (rc != 0) return rc;
-        a.in_packed = 0;
+void add_ssf_wave_kernels(KernelTable& scan, KernelTable& lut) {
+#define QDEC_SHAPE(R, V, D)              \
+    if (!find_kernel(scan, {1, V, R})) { \
+        add_ssf<1, R, V>(scan, lut);     \
+        add_ssf<2, R, V>(scan, lut);     \
     }
-    if (p.bp >= kBpGroup) return launch_decode_block(g, p, a, num_cus, stream, scratch, scratch_bytes);
-    return launch_wave(g, p, a, num_cus, stream, triaged);
-}
-
-#ifdef QDEC_STAMPS
-extern "C" __attribute__((visibility("default"))) int qd_dev_read_stamps(unsigned long long* out, int n, int reset) {
-    unsigned long long h[64] = {0};
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(qdec_stamps), sizeof(h)) != hipSuccess) return -1;
-    for (int i = 0; i < n && i < 64; ++i) out[i] = h[i];
-    if (reset) {
-        unsigned long long z[64] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(qdec_stamps), z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
-
-// ---------------------------------------------------------------- flag counter
-__global__ void count_flags_kernel(const uint8_t* __restrict__ f, int64_t B, uint8_t mask,
-                                   unsigned long long* out) {
-    long long local = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < B; i += (int64_t)gridDim.x * blockDim.x)
-        local += (f[i] & mask) ? 1 : 0;
-    local = wave_sum_i32((int)local);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(out, (unsigned long long)local);
-}
-
-int launch_count_flags(const uint8_t* flags, int64_t B, uint8_t mask, int64_t* out, hipStream_t stream) {
-    if (B <= 0) return 0;
-    long long blocks = (B + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(count_flags_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, flags, B, mask,
-                       reinterpret_cast<unsigned long long*>(out));
-    return (int)hipGetLastError();
+    QDEC_WAVE_SHAPES(QDEC_SHAPE)
+#undef QDEC_SHAPE
 }
 
 }  // namespace qdec

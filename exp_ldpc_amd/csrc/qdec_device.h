@@ -1,5 +1,6 @@
-// qdec_device.h -- device helpers shared by the wave kernels (qdec_bp.hip) and
-// the workgroup kernels (qdec_bp_block.hip).
+// qdec_device.h -- device helpers shared by the kernel units of the wave graphs
+// and of the workgroup graphs (device code only; the host side of a launch is
+// qdec_kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,19 @@ static __device__ unsigned long long qdec_stamps[64];
         if ((threadIdx.x & 63) == 0)                                          \
             for (int qdec_k_ = 0; qdec_k_ < 16; ++qdec_k_) atomicAdd(&qdec_stamps[(off) + qdec_k_], qdec_acc_[qdec_k_]); \
     } while (0)
+// A unit's reader of its own qdec_stamps (the array is per translation unit):
+// adds the 64 slots to out[0..63] and clears them when reset != 0.  The exports
+// (qd_dev_read_stamps: the wave units; qd_dev_read_stamps_block) sum their
+// units' readers.  Only units that use QDEC_STAMP / QDEC_FLUSH_AT define one.
+#define QDEC_STAMPS_READER(name)                                                                 \
+    int name(unsigned long long* out, int reset) {                                               \
+        unsigned long long h[64] = {0};                                                          \
+        if (hipMemcpyFromSymbol(h, HIP_SYMBOL(qdec_stamps), sizeof(h)) != hipSuccess) return -1; \
+        for (int i = 0; i < 64; ++i) out[i] += h[i];                                             \
+        if (!reset) return 0;                                                                    \
+        for (int i = 0; i < 64; ++i) h[i] = 0;                                                   \
+        return hipMemcpyToSymbol(HIP_SYMBOL(qdec_stamps), h, sizeof(h)) != hipSuccess ? -1 : 0;  \
+    }
 #else
 #define QDEC_STAMP_DECL
 #define QDEC_STAMP(k) \
@@ -40,6 +54,7 @@ static __device__ unsigned long long qdec_stamps[64];
 #define QDEC_FLUSH_AT(off) \
     do {                   \
     } while (0)
+#define QDEC_STAMPS_READER(name)
 #endif
 
 // Parity of popc(X & M) over NW 64-bit words, X wave-uniform (ballot words).
@@ -600,45 +615,6 @@ __device__ inline void queue_push_packed(const DecodeArgs& a, int64_t shot, cons
         hi = lane == 1 + XW + w ? (uint32_t)(rw[w] >> 32) : hi;
     }
     if (lane < QW) a.q_w[(int64_t)slot * QW + lane] = ((uint64_t)hi << 32) | lo;
-}
-
-// ---------------------------------------------------------------- resident grids
-// Every persistent kernel is launched with as many workgroups as stay resident:
-// raise the dynamic-LDS limit when the request needs it, ask the occupancy,
-// apply the launcher's cap per CU, clamp to the work items.  *grid <= 0: nothing
-// to launch.
-struct GridRule {
-    int cap_per_cu = 0;  // > 0: at most this many workgroups per CU
-    // one-wave blocks: a multiple of 4 per CU puts the same number of waves on
-    // every SIMD (11 f64 waves would sit 3/3/3/2 and run slower than 8)
-    bool whole_simds = false;
-};
-template <typename K>
-inline hipError_t resident_grid(K kern, int block, size_t lds, int num_cus, long long work, long long* grid,
-                                GridRule rule = {}) {
-    if (lds > 64 * 1024) {
-        const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return ea;
-    }
-    int per_cu = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, block, lds);
-    if (e != hipSuccess) return e;
-    if (per_cu <= 0) return hipErrorInvalidConfiguration;
-    if (rule.cap_per_cu > 0 && per_cu > rule.cap_per_cu) per_cu = rule.cap_per_cu;
-    if (rule.whole_simds && block == 64 && per_cu > 4) per_cu &= ~3;
-    *grid = std::min((long long)num_cus * per_cu, work);
-    return hipSuccess;
-}
-template <typename K, typename... A>
-inline int launch_resident(K kern, int block, size_t lds, int num_cus, long long work, hipStream_t stream,
-                           GridRule rule, const A&... args) {
-    long long grid = 0;
-    const hipError_t e = resident_grid(kern, block, lds, num_cus, work, &grid, rule);
-    if (e != hipSuccess) return (int)e;
-    if (grid <= 0) return 0;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds, stream, args...);
-    return (int)hipGetLastError();
 }
 
 }  // namespace qdec

@@ -1,5 +1,5 @@
 // qdec_graph.h -- the graph description the host table builders (qdec_tables.cpp)
-// fill and the kernels (qdec_bp.hip, qdec_sample.hip) read.  No HIP type: the
+// fill and the kernels (the kernel units, qdec_sample.hip) read.  No HIP type: the
 // builders compile without the HIP headers; qdec_internal.h adds the launch side.
 #pragma once
 #include <stdint.h>
@@ -96,7 +96,7 @@ struct DevGraph {
     const void* ms_state0[2];     // [precision][m_pad][2]
     int ms_d3r;                   // leading 64-slot rounds whose variables all have degree <= 3
     int ms_allpos;                // bit p: every prior LLR of precision p is > 0
-    // iteration 1 of min-sum inside the triage (ms_triage_kernel, qdec_bp_ms.h):
+    // iteration 1 of min-sum inside the triage (ms_triage_kernel, qdec_ms_triage.hip):
     // the checks of column j's edges in edge order (4 x u16, pad -> m), the
     // columns of check i's row (8 x u16 over two words, pad -> n), and per
     // precision each column's hard decision after iteration 1 as a 16-bit table
@@ -106,7 +106,7 @@ struct DevGraph {
     const uint64_t* it1_cvar;     // [m_pad][2]
     const uint16_t* it1_lut[2];   // [precision][n_pad]
     int wave_occ;                 // qd_graph_set_wave_occupancy (0: default)
-    // LDS-resident min-sum workgroup kernel (qdec_bp_block.hip, bp_ms_lds_kernel):
+    // LDS-resident min-sum workgroup kernel (qdec_ms_lds.hip, bp_ms_lds_kernel):
     // [kMlDC][n] LDS element of edge k of column j (row * kMlDRS + CSR position),
     // pad 0xffff; nullptr when the graph's degrees exceed kMlDRS / kMlDC
     const uint16_t* ml_etab;

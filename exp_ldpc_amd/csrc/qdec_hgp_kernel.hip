@@ -24,7 +24,7 @@
 //   variable: prefix sums from the prior in ascending check order, each
 //          outgoing message = prefix + (sum of the later c2v, accumulated
 //          from the end); hard decision acc <= 0
-//   sign tests by sign bits with MsCore's zero rule (qdec_bp_ms.h:76-118): a
+//   sign tests by sign bits with MsCore's zero rule (qdec_bp_ms.h, "Sign-bit tests"): a
 //   half holding a zero entry (its m1 == 0, rare, a divergent branch) takes its
 //   parity from compares, and flags a +0 in its m2's sign so the merged m2
 //   carries parity ^ (+0 present).

@@ -1,5 +1,5 @@
 // qdec_internal.h -- launch arguments and launchers shared by the host ABI
-// (qdec_abi.cpp) and the kernels (qdec_bp.hip, qdec_sample.hip); the graph
+// (qdec_abi.cpp) and the kernel and launch units (qdec_launch_wave.hip, qdec_sample.hip, ...); the graph
 // description they work on is qdec_graph.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -43,7 +43,7 @@ struct DecodeArgs {
     // nullptr -> static stride.  Set by the launcher.
     unsigned long long* work_ctr;
     // min-sum wave kernel: counter of the dynamically scheduled shot chunks
-    // (ShotSeq, qdec_bp_ms.h); zeroed by the launcher; nullptr -> static stride
+    // (ShotSeq, qdec_shot_seq.h); zeroed by the launcher; nullptr -> static stride
     unsigned long long* wave_ctr;
     // SSF on a second stream (qd_graph_set_ssf_stream, wave kernels only): the
     // SSF kernel waits for ssf_ev (recorded after the BP kernel) on ssf_stream,
@@ -114,8 +114,8 @@ inline void record_ev(const DecodeArgs& a, int i, hipStream_t s) {
 }
 
 // One built instantiation of a kernel family: what a launch needs to know about
-// it.  The families' tables (wave_tables in qdec_bp.hip, block_tables in
-// qdec_bp_block.hip) list every instantiation the library builds; plan_decode
+// it.  The families' tables (wave_tables in qdec_launch_wave.hip, block_tables in
+// qdec_launch_block.hip) list every instantiation the library builds; plan_decode
 // picks the entries of a decode, the launchers launch what the plan holds.
 struct KernelEntry {
     const void* fn = nullptr;  // host address of the kernel (hipLaunchKernel, hipFuncSetAttribute)
@@ -198,7 +198,7 @@ struct DecodePlan {
 // (which buffers are present, syn_flags, in_packed, ssf, max_iter, ms_scaling,
 // the alignment of syn / readout); no HIP call, so host-only graphs plan too.
 DecodePlan plan_decode(const DevGraph& g, int method, int precision, const DecodeArgs& a);
-// the workgroup half (qdec_bp_block.hip): graphs no wave shape holds
+// the workgroup half (qdec_launch_block.hip): graphs no wave shape holds
 void plan_decode_block(const DevGraph& g, const DecodeArgs& a, DecodePlan& p);
 // SSF + finalize of queued shots by a workgroup kernel with its state in LDS
 int ssf_fin_path(const DevGraph& g, const DecodeArgs& a);
@@ -209,7 +209,7 @@ bool wave_kernel_supports(const DevGraph& g);
 // so the byte-row triage can load them)
 inline size_t unpack_region(int64_t B, int cols) { return ((size_t)B * cols + 15) / 16 * 16; }
 
-// Launchers (qdec_bp.hip / qdec_sample.hip).  Return hipError_t as int.
+// Launchers (qdec_launch_wave.hip, qdec_launch_block.hip, qdec_sample.hip).  Return hipError_t as int.
 // *triaged: the two-pass path's triage was enqueued (it zeroed the other
 // counter set of the handle)
 int launch_decode(const DevGraph& g, const DecodePlan& p, const DecodeArgs& a, int num_cus, hipStream_t stream,

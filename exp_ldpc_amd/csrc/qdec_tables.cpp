@@ -20,7 +20,7 @@ int drs() { return lds_stride<T, kDR>(); }
 template <typename T>
 int dcs() { return lds_stride<T, kDC>(); }
 
-// Check-state slots of bp_ms_lds64_kernel (f64, one shot per CU; qdec_bp_block.hip).
+// Check-state slots of bp_ms_lds64_kernel (f64, one shot per CU; qdec_ms_lds64.hip).
 // Its variable thread t owns columns r * 1024 + (67 t mod 1024); per (wave,
 // round r, edge k) one LDS instruction of 64 lanes reads or atomically updates
 // the state of each lane's k-th check.  The banking gfx950 applies

@@ -106,7 +106,7 @@ void sample_tables_copy(const HostGraph* G, uint32_t* thr, int32_t* crow);
 void ssf_tables_copy(const DevGraph& g, uint32_t* lut, uint32_t* off, uint32_t* lcw, uint32_t* tog, int32_t* g_pad,
                      int32_t* m_pad);
 
-// Words of a compact-list entry (wave graphs; qdec_bp_ms.h CmpEntry): shot,
+// Words of a compact-list entry (wave graphs; qdec_cmp_list.h CmpEntry): shot,
 // syndrome words, readout logical-parity words.
 size_t cmp_entry_bytes(const DevGraph& g);
 
