@@ -84,6 +84,7 @@ SIGNATURES = {
     "qd_graph_read_timing_detail": (_i32, [_p, _p, _p, _p, _p, _i32, C.POINTER(_i32)]),
     "qd_graph_last_kernels": (_i32, [_p, C.c_char_p, _i32, C.c_char_p, _i32, C.c_char_p, _i32]),
     "qd_osd_device_supported": (_i32, [_p]),
+    "qd_osd_kernel_info": (_i32, [_p, _p]),
     "qd_osd_batch_device": (_i32, [_p, _i32, _i32, _i64, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "qd_graph_set_option": (_i32, [_p, _i32, _i32]),
     "qd_graph_get_option": (_i32, [_p, _i32, C.POINTER(_i32)]),

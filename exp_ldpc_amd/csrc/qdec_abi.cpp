@@ -836,6 +836,17 @@ int qd_osd_device_supported(const qd_graph* G) {
     return osd_kernel_supports(G->dg) ? 1 : 0;
 }
 
+int qd_osd_kernel_info(const qd_graph* G, int32_t out[3]) {
+    OsdChoice c{0, 0, 0};
+    const bool ok = G && osd_choose(G->dg, &c);
+    if (out) {
+        out[0] = c.rs;
+        out[1] = c.w;
+        out[2] = c.lds;
+    }
+    return ok ? 1 : 0;
+}
+
 int qd_osd_batch_device(qd_graph* G, int32_t method, int32_t order, int64_t B, const uint8_t* syn, int32_t syn_flags,
                         const void* llr, int32_t llr_precision, const uint8_t* status, const uint8_t* base,
                         const uint8_t* readout, uint8_t* osd0_out, uint8_t* osdw_out, uint8_t* corr_out, uint8_t* fail,

@@ -102,6 +102,15 @@ struct OsdArgs {
     uint8_t* corr_out;       // [B][n_data] nullable: base ^ fold(osdw)
     uint8_t* fail;           // [B] nullable: any(Lz (readout ^ corr))
 };
+// Which OSD kernel holds a graph, by m, n (and k) alone: rs = row slots and w =
+// row words of the register kernel osd_wave_kernel<rs, w>, or rs = 0 and w = the
+// row words of the workgroup kernel; lds = the launch's dynamic LDS bytes.
+// False (all zero): no device kernel.  No HIP call; launch_osd launches what it
+// answers.
+struct OsdChoice {
+    int rs, w, lds;
+};
+bool osd_choose(const DevGraph& g, OsdChoice* c);
 bool osd_kernel_supports(const DevGraph& g);
 int launch_osd(const DevGraph& g, const OsdArgs& a, int num_cus, hipStream_t stream);
 

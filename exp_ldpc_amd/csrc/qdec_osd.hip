@@ -30,6 +30,7 @@
 
 #include "qdec_device.h"
 #include "qdec_internal.h"
+#include "qdec_kernels.h"
 
 namespace qdec {
 
@@ -723,16 +724,12 @@ __global__ __launch_bounds__(kOsdBlock) void osd_block_kernel(DevGraph g, OsdArg
 
 namespace {
 template <int RS, int W>
-int launch_osd_shape(const DevGraph& g, const OsdArgs& a, int num_cus, hipStream_t stream) {
-    const OsdLayout L(g.n, g.m, RS, W);
-    int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osd_wave_kernel<RS, W>, 64, L.total);
+int launch_osd_shape(const DevGraph& g, const OsdArgs& a, int lds, int num_cus, hipStream_t stream) {
+    long long grid = 0;
+    const hipError_t e = resident_grid(osd_wave_kernel<RS, W>, 64, (size_t)lds, num_cus, a.B, &grid);
     if (e != hipSuccess) return (int)e;
-    if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-    long long grid = (long long)num_cus * per_cu;
-    if (grid > a.B) grid = a.B;
     if (grid <= 0) return 0;
-    hipLaunchKernelGGL((osd_wave_kernel<RS, W>), dim3((unsigned)grid), dim3(64), L.total, stream, g, a);
+    hipLaunchKernelGGL((osd_wave_kernel<RS, W>), dim3((unsigned)grid), dim3(64), lds, stream, g, a);
     return (int)hipGetLastError();
 }
 }  // namespace
@@ -741,45 +738,51 @@ int launch_osd_shape(const DevGraph& g, const OsdArgs& a, int num_cus, hipStream
 
 static int osd_row_slots(int m) { return m <= 128 ? 2 : (m <= 256 ? 4 : 6); }
 
-static bool osd_wave_supports(const DevGraph& g) {
-    if (g.m <= 0 || g.m > 384 || g.n + 1 > 1024) return false;
-    const int rs = osd_row_slots(g.m);
-    const int need = (g.n + 1 + 63) / 64;
-#define QDEC_OSD_FITS(R, V) if (rs == R && need <= V) return true;
-    QDEC_OSD_SHAPES(QDEC_OSD_FITS)
+// The one place that decides which OSD kernel holds a graph (launch_osd and
+// qd_osd_kernel_info both ask it; no HIP call).  Register kernel: RS by m, W the
+// first built width >= ceil((n + 1) / 64).  Otherwise the workgroup kernel
+// (rs = 0, w = its row words) while its LDS image fits one CU's 160 KiB and the
+// indices fit 16 bits.
+bool osd_choose(const DevGraph& g, OsdChoice* c) {
+    *c = OsdChoice{0, 0, 0};
+    if (g.m <= 0 || g.n <= 0) return false;
+    if (g.m <= 384 && g.n + 1 <= 1024) {
+        const int rs = osd_row_slots(g.m);
+        const int need = (g.n + 1 + 63) / 64;
+#define QDEC_OSD_FITS(R, V)                                    \
+    if (rs == R && need <= V) {                                \
+        *c = OsdChoice{R, V, OsdLayout(g.n, g.m, R, V).total}; \
+        return true;                                           \
+    }
+        QDEC_OSD_SHAPES(QDEC_OSD_FITS)
 #undef QDEC_OSD_FITS
-    return false;
+    }
+    if (g.n >= 65535 || g.m >= 65535 || g.k > 256) return false;
+    const OsdBlockLayout L(g.n, g.m);
+    if (L.total > 160 * 1024) return false;
+    *c = OsdChoice{0, L.W, L.total};
+    return true;
 }
 
-// the workgroup variant: its LDS image within one CU's 160 KiB, 16-bit indices
-static bool osd_block_supports(const DevGraph& g) {
-    if (g.m <= 0 || g.n <= 0 || g.n >= 65535 || g.m >= 65535) return false;
-    return OsdBlockLayout(g.n, g.m).total <= 160 * 1024 && g.k <= 256;
+bool osd_kernel_supports(const DevGraph& g) {
+    OsdChoice c;
+    return osd_choose(g, &c);
 }
-
-bool osd_kernel_supports(const DevGraph& g) { return osd_wave_supports(g) || osd_block_supports(g); }
 
 int launch_osd(const DevGraph& g, const OsdArgs& a, int num_cus, hipStream_t stream) {
     if (a.B <= 0) return 0;
-    if (!osd_wave_supports(g)) {
-        if (!osd_block_supports(g)) return (int)hipErrorNotSupported;
-        const OsdBlockLayout L(g.n, g.m);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&osd_block_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
+    OsdChoice c;
+    if (!osd_choose(g, &c)) return (int)hipErrorNotSupported;
+    if (c.rs == 0) {
+        long long grid = 0;
+        const hipError_t e = resident_grid(osd_block_kernel, kOsdBlock, (size_t)c.lds, num_cus, a.B, &grid);
         if (e != hipSuccess) return (int)e;
-        int per_cu = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osd_block_kernel, kOsdBlock, L.total);
-        if (e != hipSuccess) return (int)e;
-        if (per_cu <= 0) return (int)hipErrorInvalidConfiguration;
-        long long grid = (long long)num_cus * per_cu;
-        if (grid > a.B) grid = a.B;
-        hipLaunchKernelGGL(osd_block_kernel, dim3((unsigned)grid), dim3(kOsdBlock), L.total, stream, g, a);
+        if (grid <= 0) return 0;
+        hipLaunchKernelGGL(osd_block_kernel, dim3((unsigned)grid), dim3(kOsdBlock), c.lds, stream, g, a);
         return (int)hipGetLastError();
     }
-    const int rs = osd_row_slots(g.m);
-    const int need = (g.n + 1 + 63) / 64;
 #define QDEC_OSD_LAUNCH(R, V) \
-    if (rs == R && need <= V) return launch_osd_shape<R, V>(g, a, num_cus, stream);
+    if (c.rs == R && c.w == V) return launch_osd_shape<R, V>(g, a, c.lds, num_cus, stream);
     QDEC_OSD_SHAPES(QDEC_OSD_LAUNCH)
 #undef QDEC_OSD_LAUNCH
     return (int)hipErrorNotSupported;

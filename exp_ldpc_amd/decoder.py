@@ -290,6 +290,12 @@ class Decoder:
     def osd_device_supported(self) -> bool:
         return bool(self._lib.qd_osd_device_supported(self._handle))
 
+    def osd_kernel_info(self):
+        """(RS, W, dynamic LDS bytes) of the kernel osd_device launches for this
+        graph (qd_osd_kernel_info; RS = 0: the workgroup kernel), or None when
+        no device kernel holds it.  No launch."""
+        return osd_kernel_info(self._handle)
+
     def osd_device(self, B: int, *, llr, method: str = "osd_cs", order: int = 0, syn=None, syn_flags: int = 0,
                    status=None, base=None, readout=None, osd0=None, osdw=None, corr=None, fail=None,
                    stream=None) -> None:
@@ -410,6 +416,15 @@ class Decoder:
 
 
 QD_INPUT_PACKED = _abi.QD_INPUT_PACKED  # qd_syn_flags: bit-packed input rows
+
+
+def osd_kernel_info(handle):
+    """Decoder.osd_kernel_info for a raw qd_graph handle (a host-only graph of
+    qd_graph_create_host included)."""
+    out = np.zeros(3, np.int32)
+    if not _abi.load().qd_osd_kernel_info(handle, _abi.ptr(out)):
+        return None
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def pack_rows(bits) -> np.ndarray:

@@ -1,8 +1,9 @@
 """Ordered-statistics decoding stage, host side (C++ in libqdec_hip.so,
 qd_osd_batch).  The batched pipelines use the GPU version
 (Decoder.osd_device -> qd_osd_batch_device, csrc/qdec_osd.hip, bit-identical)
-whenever the graph fits it (m <= 384, n < 1024); this host stage serves the
-single-shot ldpc-compatible API and larger graphs.
+whenever a device kernel holds the graph (Decoder.osd_device_supported: rows in
+registers for m <= 384 and n < 1024, rows in LDS up to a 160 KiB image); this
+host stage serves the single-shot ldpc-compatible API and larger graphs.
 
 Post-processes the BP soft output of shots BP did not converge on, as ldpc v1's
 ``bposd_decoder`` does (reference call sites python/qldpc/misc/_experiment.py:23,

@@ -204,8 +204,16 @@ const char* qd_osd_last_error(void);
  * qd_decode_batch).  Outputs for processed shots (each nullable): osd0_out,
  * osdw_out [B][n] (ldpc .osd0_decoding / .osdw_decoding), corr_out = base ^
  * fold(osdw), fail = any(Lz (readout ^ corr_out)).  Bit-identical to
- * qd_osd_batch.  Needs m <= 384 and n < 1024 (qd_osd_device_supported). */
+ * qd_osd_batch.  Needs a graph a device kernel holds (qd_osd_device_supported):
+ * m <= 384 and n < 1024 for the register kernel, an LDS image of at most 160 KiB
+ * for the workgroup kernel; otherwise -85. */
 int qd_osd_device_supported(const qd_graph* g);
+/* Which kernel qd_osd_batch_device launches for the graph, decided by the code
+ * the launch itself uses; no HIP call, so host-only graphs (qd_graph_create_host)
+ * answer too.  out[0] = RS and out[1] = W of osd_wave_kernel<RS, W> (RS = 0: the
+ * workgroup kernel, W = its words per row), out[2] = the launch's dynamic LDS
+ * bytes.  Returns 1, or 0 (out all zero) when no device kernel holds the graph. */
+int qd_osd_kernel_info(const qd_graph* g, int32_t out[3]);
 int qd_osd_batch_device(qd_graph* g, int32_t method, int32_t order, int64_t B, const uint8_t* syn, int32_t syn_flags,
                         const void* llr, int32_t llr_precision, const uint8_t* status, const uint8_t* base,
                         const uint8_t* readout, uint8_t* osd0_out, uint8_t* osdw_out, uint8_t* corr_out, uint8_t* fail,

@@ -4,7 +4,8 @@ Same spec as exp_ldpc_amd/csrc/qdec_osd.cpp (this build's restatement of ldpc
 v1's published OSD-0 / OSD-E / OSD-CS; ldpc itself is absent, so parity against
 it is unpinned), written independently: column order by a stable argsort of the
 BP log-probability ratios, plain row reduction on a dense uint8 matrix, and
-candidates solved from scratch (no transform reuse).  Small cases only.
+every candidate's pivot bits solved through one row transform of the pivot
+columns (a dense product, no reuse of the reduced matrix).  Small cases only.
 """
 from __future__ import annotations
 
@@ -62,13 +63,22 @@ def _reduce(Hs):
 
 def osd_decode(H, syndrome, llr, method="osd_cs", order=0):
     """Returns (osd0, osdw) uint8[n]."""
+    return osd_decode_methods(H, syndrome, llr, [(method, order)])[0]
+
+
+def osd_decode_methods(H, syndrome, llr, methods):
+    """[(osd0, osdw)] of one shot, one pair per (method, order) in `methods`: the
+    column order, the pivots and the row transform do not depend on the method
+    and are computed once."""
     H = sp.csr_matrix(H).toarray() % 2
     m, n = H.shape
     cols = np.argsort(np.asarray(llr, dtype=np.float64), kind="stable")
     Hs = H[:, cols]
     s = np.asarray(syndrome, dtype=np.uint8) % 2
     piv, x0p = _solve_pivots(Hs, s)
-    nonpiv = [c for c in range(n) if c not in set(piv)]
+    pivset = set(piv)
+    nonpiv = [c for c in range(n) if c not in pivset]
+    r = len(piv)
 
     def assemble(xp, g):
         xs = np.zeros(n, np.uint8)
@@ -80,30 +90,38 @@ def osd_decode(H, syndrome, llr, method="osd_cs", order=0):
         return out
 
     osd0 = assemble(x0p, [])
-    if method == "osd0":
-        return osd0, osd0.copy()
-    best = osd0
-    best_w = int(osd0.sum())
-    lam = min(order, len(nonpiv))
-    if method == "osd_e":
-        cands = []
-        for mask in range(1, 1 << lam):
-            cands.append([nonpiv[t] for t in range(lam) if (mask >> t) & 1])
-    else:
-        cands = [[c] for c in nonpiv] + [[nonpiv[a], nonpiv[b]] for a, b in itertools.combinations(range(lam), 2)]
-    if not cands:
-        return osd0, best
-    # every candidate's pivot solution from one row transform of Hs[:, piv]
-    # (full column rank), in candidate order; strict improvement keeps the earlier
-    piv2, T = _reduce(Hs[:, piv])
-    assert piv2 == list(range(len(piv)))
-    r = len(piv)
-    S2 = np.repeat(s[:, None], len(cands), axis=1).astype(np.int64)
-    for ci, g in enumerate(cands):
-        S2[:, ci] += Hs[:, g].astype(np.int64).sum(axis=1)
-    XP = (T.astype(np.int64) @ (S2 % 2)) % 2
-    for ci, g in enumerate(cands):
-        w = int(XP[:r, ci].sum()) + len(g)
-        if w < best_w:
-            best, best_w = assemble(XP[:r, ci].astype(np.uint8), g), w
-    return osd0, best
+    T = None
+    res = []
+    for method, order in methods:
+        if method == "osd0":
+            res.append((osd0, osd0.copy()))
+            continue
+        lam = min(order, len(nonpiv))
+        if method == "osd_e":
+            cands = []
+            for mask in range(1, 1 << lam):
+                cands.append([nonpiv[t] for t in range(lam) if (mask >> t) & 1])
+        else:
+            cands = [[c] for c in nonpiv] + [[nonpiv[a], nonpiv[b]] for a, b in itertools.combinations(range(lam), 2)]
+        if not cands:
+            res.append((osd0, osd0))
+            continue
+        # every candidate's pivot solution from one row transform of Hs[:, piv]
+        # (full column rank).  0/1 entries and sums <= max(m, n): exact in float64
+        if T is None:
+            piv2, T = _reduce(Hs[:, piv])
+            assert piv2 == list(range(r))
+            T = T.astype(np.float64)
+        sizes = np.array([len(g) for g in cands])
+        sel = sp.csr_matrix((np.ones(sizes.sum()), np.concatenate(cands), np.concatenate([[0], np.cumsum(sizes)])),
+                            shape=(len(cands), n))  # row ci: the candidate's columns
+        S2 = s[:, None] + (sel @ Hs.T.astype(np.float64)).T  # column ci = s + the sum of those columns of Hs
+        XP = ((T @ (S2 % 2)) % 2).astype(np.uint8)
+        # least weight wins, an earlier candidate keeps a tie, osd0 before all
+        wts = XP[:r].sum(axis=0, dtype=np.int64) + sizes
+        ci = int(np.argmin(wts))
+        if wts[ci] < int(osd0.sum()):
+            res.append((osd0, assemble(XP[:r, ci], cands[ci])))
+        else:
+            res.append((osd0, osd0))
+    return res
