@@ -1155,3 +1155,109 @@ int qd_count_flags_device(const uint8_t* flags, int64_t B, uint8_t mask, int64_t
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- compiled circuits
+// A validated Pauli-frame program (qdec_circuit.h) and, unless host-only, its
+// copy on one device.
+struct qd_circuit {
+    HostCircuit hc;
+    DevCircuit dc{};
+    bool host_only = true;
+    int device = 0;
+    int num_cus = 0;
+    DeviceSink arena;
+};
+
+namespace {
+
+int create_circuit(bool host_only, int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
+                   int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
+                   const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out) {
+    return guarded([&] {
+        if (!out) throw Fail(-71, "circuit: null output handle");
+        *out = nullptr;
+        std::unique_ptr<qd_circuit> C(new qd_circuit());
+        build_circuit(C->hc, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows, row_ptr,
+                      rec_idx);
+        C->host_only = host_only;
+        const HostCircuit& h = C->hc;
+        DevCircuit& d = C->dc;
+        d.Q = h.Q, d.M = h.M, d.n_ops = (int32_t)h.ops.size();
+        for (int g = 0; g < kFrameGroups; ++g) d.rows[g] = h.rows[g], d.row_off[g] = h.row_off[g];
+        if (!host_only) {
+            int ndev = 0;
+            hip_check(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
+            if (device < 0 || device >= ndev) throw Fail(-15, "device ordinal out of range");
+            C->device = device;
+            hip_check(hipSetDevice(device), "hipSetDevice");
+            hipDeviceProp_t prop;
+            hip_check(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties");
+            C->num_cus = prop.multiProcessorCount;
+            d.ops = static_cast<const FrameOpRec*>(C->arena.put(h.ops.data(), h.ops.size() * sizeof(FrameOpRec)));
+            d.targets = static_cast<const int32_t*>(C->arena.put(h.targets.data(), h.targets.size() * 4));
+            d.row_ptr = static_cast<const int32_t*>(C->arena.put(h.row_ptr.data(), h.row_ptr.size() * 4));
+            d.rec_idx = static_cast<const int32_t*>(C->arena.put(h.rec_idx.data(), h.rec_idx.size() * 4));
+        }
+        *out = C.release();
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int qd_circuit_create(int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
+                      const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
+                      const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out) {
+    return create_circuit(false, device, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows,
+                          row_ptr, rec_idx, out);
+}
+
+int qd_circuit_create_host(int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
+                           const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
+                           const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out) {
+    return create_circuit(true, 0, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows, row_ptr,
+                          rec_idx, out);
+}
+
+int qd_circuit_destroy(qd_circuit* C) {
+    return guarded([&] {
+        if (!C) return;
+        if (!C->host_only) (void)hipSetDevice(C->device);
+        delete C;  // its sink frees the uploads
+    });
+}
+
+int qd_circuit_info(const qd_circuit* C, int64_t out[10]) {
+    return guarded([&] {
+        if (!C || !out) throw Fail(-71, "circuit: null handle or output");
+        const HostCircuit& h = C->hc;
+        out[0] = h.Q, out[1] = h.M;
+        for (int g = 0; g < kFrameGroups; ++g) out[2 + g] = h.rows[g];
+        out[6] = (int64_t)h.lds_bytes, out[7] = (int64_t)h.ops.size(), out[8] = h.n_sites, out[9] = h.n_rsites;
+    });
+}
+
+int qd_circuit_sample_device(qd_circuit* C, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
+                             int32_t flags, void* const outs[4], void* stream) {
+    return guarded([&] {
+        if (!C) throw Fail(-71, "circuit: null handle");
+        if (C->host_only) throw Fail(-79, "host-only circuit (qd_circuit_create_host): no device to sample on");
+        if (B < 0 || (flags & ~QD_INPUT_PACKED)) throw Fail(-77, "invalid circuit sampler arguments");
+        if (B == 0) return;
+        if (!outs) throw Fail(-77, "invalid circuit sampler arguments: null output list");
+        const bool packed = (flags & QD_INPUT_PACKED) != 0;
+        void* o[kFrameGroups];
+        for (int g = 0; g < kFrameGroups; ++g) {
+            o[g] = outs[g];
+            if (o[g] && g >= C->hc.n_groups) throw Fail(-77, "output buffer for a group the circuit does not have");
+            if (packed && ((uintptr_t)o[g] & 7)) throw Fail(-78, "packed rows must be 8-B aligned");
+        }
+        hip_check(hipSetDevice(C->device), "hipSetDevice");
+        const int rc = launch_frame_sample(C->dc, C->hc.lds_bytes, seed, stream_id, shot0, B, packed, o, C->num_cus,
+                                           (hipStream_t)stream);
+        if (rc != 0) throw Fail(-102, std::string("sampler launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+}  // extern "C"

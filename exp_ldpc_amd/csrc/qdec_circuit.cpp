@@ -1,0 +1,97 @@
+// qdec_circuit.cpp -- validation of a compiled Pauli-frame program (HIP-free).
+// Nothing the kernel indexes with is taken on trust: every qubit, every record
+// reference and every CSR bound is checked here, once, at create.
+#include "qdec_circuit.h"
+
+#include <string>
+
+#include "qdec_tables.h"
+
+namespace qdec {
+
+void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
+                   const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
+                   const int32_t* row_ptr, const int32_t* rec_idx) {
+    if (num_qubits < 1 || num_qubits > kFrameQubitMask || n_ops < 0 || n_targets < 0 || n_groups < 0 ||
+        n_groups > kFrameGroups)
+        throw Fail(-71, "circuit: bad sizes (1 <= qubits, 0 <= ops, targets, 0 <= groups <= 4)");
+    if ((n_ops && (!ops || !probs)) || (n_targets && !targets) || (n_groups && (!group_rows || !row_ptr)))
+        throw Fail(-71, "circuit: null program array");
+    c.Q = num_qubits;
+    c.ops.clear();
+    c.ops.reserve(n_ops);
+    c.targets.assign(targets, targets + n_targets);
+    std::vector<int32_t> seen(num_qubits, -1);  // the last op that touched a qubit
+    uint64_t site = 0, rsite = 0, rec = 0;
+    for (int32_t i = 0; i < n_ops; ++i) {
+        const int32_t op = ops[4 * i], off = ops[4 * i + 1], cnt = ops[4 * i + 2];
+        const std::string at = " (instruction " + std::to_string(i) + ")";
+        if (op < 0 || op >= FO_COUNT) throw Fail(-71, "circuit: unknown opcode" + at);
+        if (off < 0 || cnt < 0 || (int64_t)off + cnt > n_targets) throw Fail(-71, "circuit: target range outside the target array" + at);
+        const bool pair = op == FO_CX || op == FO_CZ || op == FO_DEP2;
+        if (pair && (cnt & 1)) throw Fail(-71, "circuit: odd target count of a two-qubit instruction" + at);
+        const bool meas = op == FO_M || op == FO_MX;
+        const bool noise = op >= FO_XERR;
+        const double p = probs[i];
+        if (noise || meas) {
+            if (!(p >= 0.0 && p <= 1.0)) throw Fail(-75, "circuit: probability outside [0, 1]" + at);
+        } else if (p != 0.0) {
+            throw Fail(-75, "circuit: a gate or reset takes no probability" + at);
+        }
+        for (int32_t e = off; e < off + cnt; ++e) {
+            const int32_t t = targets[e];
+            if (t < 0 || (!meas && (t & kFrameInvert)) || (t & kFrameQubitMask) >= num_qubits)
+                throw Fail(-72, "circuit: qubit index out of range" + at);
+            if (!noise) {  // lanes split these targets: they must be pairwise disjoint
+                const int32_t q = t & kFrameQubitMask;
+                if (seen[q] == i) throw Fail(-74, "circuit: a qubit twice in one parallel group" + at);
+                seen[q] = i;
+            }
+        }
+        FrameOpRec r{};
+        r.op = op, r.tgt_off = off, r.tgt_cnt = cnt;
+        r.thr = bern_threshold(p);
+        r.site0 = (uint32_t)site, r.rsite0 = (uint32_t)rsite, r.rec0 = (int32_t)rec;
+        if (noise || meas) site += ((uint64_t)(op == FO_DEP2 ? cnt / 2 : cnt) + 3) / 4 * 4;
+        if (meas || op == FO_R || op == FO_RX) rsite += (uint64_t)cnt;
+        if (meas) rec += (uint64_t)cnt;
+        if (site >= (1ull << 31) || rsite >= (1ull << 31) || rec >= (1ull << 28))
+            throw Fail(-71, "circuit: too many draw sites or records");
+        c.ops.push_back(r);
+    }
+    c.M = (int32_t)rec;
+    c.n_sites = (uint32_t)site, c.n_rsites = (uint32_t)rsite;
+    c.lds_bytes = 16 * (size_t)c.Q + 8 * (size_t)c.M;
+    // output groups: rows of record parities
+    c.n_groups = n_groups;
+    int64_t total = 0;
+    for (int g = 0; g < kFrameGroups; ++g) {
+        c.rows[g] = c.row_off[g] = 0;
+        if (g >= n_groups) continue;
+        if (group_rows[g] < 0) throw Fail(-71, "circuit: negative row count of an output group");
+        c.rows[g] = group_rows[g];
+        c.row_off[g] = (int32_t)total;
+        total += group_rows[g];
+        if (total >= (1ll << 30)) throw Fail(-71, "circuit: too many output rows");
+    }
+    c.row_ptr.assign(1, 0);
+    c.rec_idx.clear();
+    if (n_groups) {
+        if (row_ptr[0] != 0) throw Fail(-71, "circuit: row_ptr[0] must be 0");
+        for (int64_t r = 0; r < total; ++r)
+            if (row_ptr[r + 1] < row_ptr[r]) throw Fail(-71, "circuit: row_ptr not monotone");
+        const int32_t nnz = row_ptr[total];
+        if (nnz && !rec_idx) throw Fail(-71, "circuit: null program array");
+        for (int32_t e = 0; e < nnz; ++e)
+            if (rec_idx[e] < 0 || rec_idx[e] >= c.M)
+                throw Fail(-73, "circuit: record reference outside [0, measurements): entry " + std::to_string(e) +
+                                    " = " + std::to_string(rec_idx[e]));
+        c.row_ptr.assign(row_ptr, row_ptr + total + 1);
+        c.rec_idx.assign(rec_idx, rec_idx + nnz);
+    }
+    if (c.lds_bytes > kFrameLdsLimit)
+        throw Fail(-76, "circuit: " + std::to_string(c.lds_bytes) + " B of LDS (16 B per qubit, 8 B per measurement) "
+                            "exceed the kernel's " + std::to_string(kFrameLdsLimit));
+}
+
+}  // namespace qdec

@@ -1,0 +1,62 @@
+// qdec_circuit.h -- the compiled Pauli-frame program of qd_circuit_* (HIP-free):
+// what the host hands over, what the validator makes of it, and what the kernel
+// (qdec_frame.hip) reads.  The conventions are DESIGN §3.4c.
+#ifndef QDEC_CIRCUIT_H
+#define QDEC_CIRCUIT_H
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+namespace qdec {
+
+// opcodes of the program (exp_ldpc_amd/circuit.py OP_*)
+enum FrameOp : int32_t {
+    FO_H = 0, FO_CX, FO_CZ, FO_R, FO_RX, FO_M, FO_MX, FO_XERR, FO_YERR, FO_ZERR, FO_DEP1, FO_DEP2, FO_COUNT
+};
+constexpr int kFrameGroups = 4;                    // output groups of one program
+constexpr size_t kFrameLdsLimit = 160 * 1024;      // the launch's dynamic LDS
+constexpr int32_t kFrameInvert = 1 << 30;          // measurement target bit: record inverted
+constexpr int32_t kFrameQubitMask = kFrameInvert - 1;
+
+// One instruction as the kernel reads it.  site0: its first Bernoulli / Pauli
+// draw site (a multiple of 4: one Philox block serves four sites); rsite0: its
+// first randomisation site; rec0: the record index of its first target.
+struct FrameOpRec {
+    int32_t op, tgt_off, tgt_cnt;
+    uint32_t thr, site0, rsite0;
+    int32_t rec0, pad;
+};
+
+struct HostCircuit {
+    int32_t Q = 0, M = 0;
+    std::vector<FrameOpRec> ops;
+    std::vector<int32_t> targets;
+    int32_t n_groups = 0;
+    int32_t rows[kFrameGroups] = {0, 0, 0, 0};     // rows of each group
+    int32_t row_off[kFrameGroups] = {0, 0, 0, 0};  // its first row in row_ptr
+    std::vector<int32_t> row_ptr, rec_idx;         // CSR over record indices, groups concatenated
+    uint32_t n_sites = 0, n_rsites = 0;
+    size_t lds_bytes = 0;                          // 16 Q + 8 M
+};
+
+// The program on the device (or, host-only, nothing): pointers into the handle's
+// uploads.
+struct DevCircuit {
+    int32_t Q, M, n_ops;
+    const FrameOpRec* ops;
+    const int32_t* targets;
+    const int32_t* row_ptr;
+    const int32_t* rec_idx;
+    int32_t rows[kFrameGroups], row_off[kFrameGroups];
+};
+
+// Validates every index of a program and derives the records, sites and the
+// LDS need (throws Fail with the ABI's code; include/qdec.h qd_circuit_create).
+// ops: [n_ops][4] = opcode, first target, target count, 0; probs: [n_ops].
+void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
+                   const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
+                   const int32_t* row_ptr, const int32_t* rec_idx);
+
+}  // namespace qdec
+#endif

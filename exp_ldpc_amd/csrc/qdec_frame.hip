@@ -1,0 +1,279 @@
+// qdec_frame.hip -- Pauli-frame sampler of a compiled circuit (qd_circuit_sample_device).
+//
+// Stim's frame simulation of the gate set the storage experiment uses (H, CX, CZ,
+// resets and measurements in Z and X, X/Y/Z_ERROR, DEPOLARIZE1/2), bit-sliced:
+// one wave runs 64 consecutive shots, and x[Q], z[Q] (the frame) and rec[M] (the
+// measurement record) are 64-bit words in LDS whose bit s is shot s of the wave.
+// The record is the flip against the noiseless reference sample; a measurement
+// target may carry an invert bit (kFrameInvert) for a reference sample of 1.
+//
+// Gates, resets and measurements: lanes split the targets of one instruction,
+// which the host compiler has made pairwise disjoint (validated at create), a
+// word operation each.  Noise sites: lane = shot; every lane draws its own u32,
+// a ballot makes the word, lane 0 XORs it into the frame (skipped when no lane
+// fired).  One workgroup is one wave, so the barrier between instructions only
+// orders the wave's own LDS traffic.
+//
+// Draws, key (seed, stream_id):
+//   Bernoulli / Pauli site s of global shot g: u = lane s % 4 of the
+//     Philox4x32-10 block with counter (s / 4, 0, g_lo, g_hi); fires when u < T.
+//     DEPOLARIZE1: Pauli 1 + floor(3 u / T) (1 = X, 2 = Y, 3 = Z); DEPOLARIZE2:
+//     code 1 + floor(15 u / T), first qubit's Pauli = code >> 2, second's =
+//     code & 3 (0 = I).  Every instruction's first site is a multiple of 4.
+//   Randomisation site r of shot g: bit g % 32 of lane (g / 32) % 4 of the block
+//     with counter (r, 1, (g / 128)_lo, (g / 128)_hi).
+// so a shot's bits depend on (seed, stream_id, site, global shot) only.
+#include <hip/hip_runtime.h>
+
+#include "qdec_internal.h"
+#include "qdec_wave_bits.h"
+
+namespace qdec {
+
+struct FrameOuts {
+    void* p[kFrameGroups];
+};
+
+// floor(c u / T) for u < T, c <= 15, exactly: the largest k with k T <= c u
+__device__ __forceinline__ uint32_t scaled_index(uint32_t u, uint32_t T, uint32_t c) {
+    const uint64_t n = (uint64_t)u * c;
+    uint32_t k = 0;
+#pragma unroll
+    for (uint32_t bit = 8; bit; bit >>= 1)
+        if ((uint64_t)(k + bit) * T <= n) k += bit;
+    return k;
+}
+
+// The 64 randomisation bits of site `rsite` for shots s0 .. s0 + 63 (s0 need
+// not be a multiple of 32: the word is cut from up to three u32 chunks of at
+// most two Philox blocks).
+__device__ __forceinline__ uint64_t rand_word(uint32_t rsite, uint64_t s0, uint32_t k0, uint32_t k1) {
+    const uint64_t c0 = s0 >> 5;  // first 32-shot chunk
+    const int off = (int)(s0 & 31), l0 = (int)(c0 & 3);
+    const uint64_t blk = c0 >> 2;
+    uint32_t a[4] = {rsite, 1u, (uint32_t)blk, (uint32_t)(blk >> 32)};
+    philox4x32_10(a, k0, k1);
+    uint32_t b[4] = {0u, 0u, 0u, 0u};
+    if (l0 >= 2) {  // chunks c0 + 1 or c0 + 2 lie in the next block (the same test in every lane)
+        b[0] = rsite, b[1] = 1u, b[2] = (uint32_t)(blk + 1), b[3] = (uint32_t)((blk + 1) >> 32);
+        philox4x32_10(b, k0, k1);
+    }
+    // chunk l0 + k of (a, b), by selects (a switch over the arrays indexes them dynamically: scratch)
+    const uint32_t a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], b0 = b[0], b1 = b[1];
+    const uint32_t w0 = l0 == 0 ? a0 : l0 == 1 ? a1 : l0 == 2 ? a2 : a3;
+    const uint32_t w1 = l0 == 0 ? a1 : l0 == 1 ? a2 : l0 == 2 ? a3 : b0;
+    const uint32_t w2 = l0 == 0 ? a2 : l0 == 1 ? a3 : l0 == 2 ? b0 : b1;
+    const uint64_t lo = (uint64_t)w0 | ((uint64_t)w1 << 32);
+    return off ? (lo >> off) | ((uint64_t)w2 << (64 - off)) : lo;
+}
+
+// x / z bit of Pauli code P (0 = I, 1 = X, 2 = Y, 3 = Z)
+__device__ __forceinline__ bool pauli_x(uint32_t P) { return P == 1u || P == 2u; }
+__device__ __forceinline__ bool pauli_z(uint32_t P) { return P >= 2u; }
+
+template <bool PACKED>
+__global__ __launch_bounds__(64) void frame_sample_kernel(DevCircuit c, uint32_t seed, uint32_t sid, int64_t shot0,
+                                                          int64_t B, FrameOuts o) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    uint64_t* x = reinterpret_cast<uint64_t*>(smem);  // [Q]
+    uint64_t* z = x + c.Q;                            // [Q]
+    uint64_t* rec = z + c.Q;                          // [M]: every word is written by its measurement
+    const int64_t waves = (B + 63) / 64;
+
+    for (int64_t w = blockIdx.x; w < waves; w += gridDim.x) {
+        const int64_t b0 = w * 64;
+        const int valid = (int)(B - b0 < 64 ? B - b0 : 64);
+        const uint64_t s0 = (uint64_t)(shot0 + b0);
+        const uint64_t shot = s0 + (uint64_t)lane;
+        const uint32_t g_lo = (uint32_t)shot, g_hi = (uint32_t)(shot >> 32);
+        for (int q = lane; q < 2 * c.Q; q += 64) x[q] = 0ull;
+        __syncthreads();
+
+        for (int i = 0; i < c.n_ops; ++i) {
+            const FrameOpRec r = c.ops[i];
+            const int32_t* tg = c.targets + r.tgt_off;
+            const int T = r.tgt_cnt;
+            switch (r.op) {
+                case FO_H:
+                    for (int e = lane; e < T; e += 64) {
+                        const int q = tg[e];
+                        const uint64_t t = x[q];
+                        x[q] = z[q];
+                        z[q] = t;
+                    }
+                    break;
+                case FO_CX:
+                    for (int e = lane; 2 * e < T; e += 64) {
+                        const int a = tg[2 * e], b = tg[2 * e + 1];
+                        x[b] ^= x[a];
+                        z[a] ^= z[b];
+                    }
+                    break;
+                case FO_CZ:
+                    for (int e = lane; 2 * e < T; e += 64) {
+                        const int a = tg[2 * e], b = tg[2 * e + 1];
+                        z[a] ^= x[b];
+                        z[b] ^= x[a];
+                    }
+                    break;
+                case FO_R:
+                case FO_RX: {
+                    uint64_t* keep = r.op == FO_R ? z : x;  // the component a reset leaves random
+                    uint64_t* clr = r.op == FO_R ? x : z;
+                    for (int e = lane; e < T; e += 64) {
+                        const int q = tg[e];
+                        clr[q] = 0ull;
+                        keep[q] = rand_word(r.rsite0 + (uint32_t)e, s0, seed, sid);
+                    }
+                    break;
+                }
+                case FO_M:
+                case FO_MX: {
+                    uint64_t* read = r.op == FO_M ? x : z;
+                    uint64_t* kick = r.op == FO_M ? z : x;
+                    for (int e = lane; e < T; e += 64) {
+                        const int t = tg[e], q = t & kFrameQubitMask;
+                        rec[r.rec0 + e] = (t & kFrameInvert) ? ~read[q] : read[q];
+                        kick[q] ^= rand_word(r.rsite0 + (uint32_t)e, s0, seed, sid);
+                    }
+                    if (r.thr) {
+                        __syncthreads();
+                        for (int e0 = 0; e0 < T; e0 += 4) {
+                            uint32_t u[4] = {r.site0 / 4u + (uint32_t)(e0 >> 2), 0u, g_lo, g_hi};
+                            philox4x32_10(u, seed, sid);
+#pragma unroll
+                            for (int l = 0; l < 4; ++l) {
+                                if (e0 + l >= T) break;
+                                const uint64_t f = __ballot(u[l] < r.thr);
+                                if (f && lane == 0) rec[r.rec0 + e0 + l] ^= f;
+                            }
+                        }
+                    }
+                    break;
+                }
+                case FO_XERR:
+                case FO_YERR:
+                case FO_ZERR:
+                    if (r.thr) {
+                        for (int e0 = 0; e0 < T; e0 += 4) {
+                            uint32_t u[4] = {r.site0 / 4u + (uint32_t)(e0 >> 2), 0u, g_lo, g_hi};
+                            philox4x32_10(u, seed, sid);
+#pragma unroll
+                            for (int l = 0; l < 4; ++l) {
+                                if (e0 + l >= T) break;
+                                const uint64_t f = __ballot(u[l] < r.thr);
+                                if (f && lane == 0) {
+                                    const int q = tg[e0 + l];
+                                    if (r.op != FO_ZERR) x[q] ^= f;
+                                    if (r.op != FO_XERR) z[q] ^= f;
+                                }
+                            }
+                        }
+                    }
+                    break;
+                case FO_DEP1:
+                    if (r.thr) {
+                        for (int e0 = 0; e0 < T; e0 += 4) {
+                            uint32_t u[4] = {r.site0 / 4u + (uint32_t)(e0 >> 2), 0u, g_lo, g_hi};
+                            philox4x32_10(u, seed, sid);
+#pragma unroll
+                            for (int l = 0; l < 4; ++l) {
+                                if (e0 + l >= T) break;
+                                const bool fired = u[l] < r.thr;
+                                if (__ballot(fired) == 0ull) continue;
+                                const uint32_t P = fired ? 1u + scaled_index(u[l], r.thr, 3u) : 0u;
+                                const uint64_t fx = __ballot(pauli_x(P)), fz = __ballot(pauli_z(P));
+                                if (lane == 0) {
+                                    const int q = tg[e0 + l];
+                                    x[q] ^= fx;
+                                    z[q] ^= fz;
+                                }
+                            }
+                        }
+                    }
+                    break;
+                case FO_DEP2:
+                    if (r.thr) {
+                        const int pairs = T / 2;
+                        for (int e0 = 0; e0 < pairs; e0 += 4) {
+                            uint32_t u[4] = {r.site0 / 4u + (uint32_t)(e0 >> 2), 0u, g_lo, g_hi};
+                            philox4x32_10(u, seed, sid);
+#pragma unroll
+                            for (int l = 0; l < 4; ++l) {
+                                if (e0 + l >= pairs) break;
+                                const bool fired = u[l] < r.thr;
+                                if (__ballot(fired) == 0ull) continue;
+                                const uint32_t code = fired ? 1u + scaled_index(u[l], r.thr, 15u) : 0u;
+                                const uint32_t Pa = code >> 2, Pb = code & 3u;
+                                const uint64_t ax = __ballot(pauli_x(Pa)), az = __ballot(pauli_z(Pa));
+                                const uint64_t bx = __ballot(pauli_x(Pb)), bz = __ballot(pauli_z(Pb));
+                                if (lane == 0) {
+                                    const int a = tg[2 * (e0 + l)], b = tg[2 * (e0 + l) + 1];
+                                    x[a] ^= ax;
+                                    z[a] ^= az;
+                                    x[b] ^= bx;
+                                    z[b] ^= bz;
+                                }
+                            }
+                        }
+                    }
+                    break;
+                default:
+                    break;
+            }
+            __syncthreads();
+        }
+
+        // outputs: row r of a group = the parity of its records, a word of 64 shots
+#pragma unroll
+        for (int g = 0; g < kFrameGroups; ++g) {
+            void* const og = o.p[g];
+            if (!og) continue;
+            const int rows = c.rows[g];
+            const int32_t* rp = c.row_ptr + c.row_off[g];
+            const int words = (rows + 63) / 64;
+            for (int j = 0; j < words; ++j) {
+                const int row = 64 * j + lane;
+                uint64_t v = 0ull;  // rows past the end: the padding bits of a packed row, written 0
+                if (row < rows)
+                    for (int e = rp[row]; e < rp[row + 1]; ++e) v ^= rec[c.rec_idx[e]];
+                if constexpr (PACKED) {
+                    const uint64_t mine = wave_transpose64(v, lane);  // lane s: shot s's word j
+                    if (lane < valid) static_cast<uint64_t*>(og)[(b0 + lane) * words + j] = mine;
+                } else {
+                    uint8_t* out = static_cast<uint8_t*>(og) + b0 * rows + row;
+                    if (row < rows)
+                        for (int s = 0; s < valid; ++s) out[(int64_t)s * rows] = (uint8_t)((v >> s) & 1ull);
+                }
+            }
+        }
+        __syncthreads();  // the frame is zeroed for the next 64 shots
+    }
+}
+
+int launch_frame_sample(const DevCircuit& c, size_t lds, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
+                        bool packed, void* const outs[kFrameGroups], int num_cus, hipStream_t stream) {
+    if (B <= 0) return 0;
+    FrameOuts o;
+    for (int g = 0; g < kFrameGroups; ++g) o.p[g] = outs[g];
+    const void* fn = packed ? reinterpret_cast<const void*>(frame_sample_kernel<true>)
+                            : reinterpret_cast<const void*>(frame_sample_kernel<false>);
+    if (lds < 16) lds = 16;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    long long grid = (long long)num_cus * 32;  // one wave per block; LDS decides how many a CU holds
+    const long long waves = (B + 63) / 64;
+    if (grid > waves) grid = waves;
+    if (packed)
+        hipLaunchKernelGGL(frame_sample_kernel<true>, dim3((unsigned)grid), dim3(64), lds, stream, c, seed, stream_id,
+                           shot0, B, o);
+    else
+        hipLaunchKernelGGL(frame_sample_kernel<false>, dim3((unsigned)grid), dim3(64), lds, stream, c, seed,
+                           stream_id, shot0, B, o);
+    return (int)hipGetLastError();
+}
+
+}  // namespace qdec

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "qdec_circuit.h"
 #include "qdec_graph.h"
 
 namespace qdec {
@@ -238,6 +239,11 @@ int launch_sample_faults(const DevGraph& g, const uint32_t* thr, const int32_t* 
                          uint32_t stream_id, int64_t shot0, int64_t B, bool packed, void* det, void* faults,
                          uint8_t* obs, int num_cus, hipStream_t stream);
 int launch_count_flags(const uint8_t* flags, int64_t B, uint8_t mask, int64_t* out, hipStream_t stream);
+// B shots of a compiled circuit (frame_sample_kernel, qdec_frame.hip): group g's
+// rows to outs[g] (nullable), byte rows or u64 words when packed; lds = the
+// program's HostCircuit::lds_bytes
+int launch_frame_sample(const DevCircuit& c, size_t lds, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
+                        bool packed, void* const outs[kFrameGroups], int num_cus, hipStream_t stream);
 
 // ---------------------------------------------------------------- HGP kernel
 // Hypergraph-product codes get their own f64 min-sum BP kernel, generated and

@@ -6,6 +6,7 @@
 #include "qdec_cmp_list.h"
 #include "qdec_device.h"
 #include "qdec_kernels.h"
+#include "qdec_wave_bits.h"
 
 namespace qdec {
 
@@ -121,24 +122,7 @@ struct TriageIt1 {
 constexpr int kT1GateW = 12;  // iteration-1 tile gate: syndrome weight bound ...
 constexpr int kT1GateN = 8;   // ... and shots of the tile within it
 constexpr int kTriageUB = 16;  // readout-tile loads per lane per round
-// 64 x 64 bit transpose across the wave: lane r holds row r (bit c = entry
-// (r, c)), and gets back column r (bit c = entry (c, r)).  Six block-swap
-// stages, each one exchange with lane ^ j: the off-diagonal j x j blocks of
-// every 2j x 2j block trade places.
-__device__ __forceinline__ uint64_t wave_transpose64(uint64_t v, int lane) {
-    const uint64_t keep[6] = {0x00000000FFFFFFFFull, 0x0000FFFF0000FFFFull, 0x00FF00FF00FF00FFull,
-                              0x0F0F0F0F0F0F0F0Full, 0x3333333333333333ull, 0x5555555555555555ull};
-#pragma unroll
-    for (int st = 0; st < 6; ++st) {
-        const int j = 32 >> st;
-        const uint64_t k0 = keep[st];  // columns c with (c & j) == 0
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, j);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), j);
-        const uint64_t w = ((uint64_t)hi << 32) | lo;
-        v = (lane & j) ? ((v & ~k0) | ((w >> j) & k0)) : ((v & k0) | ((w & k0) << j));
-    }
-    return v;
-}
+// (wave_transpose64, the 64 x 64 bit transpose across the wave: qdec_wave_bits.h)
 
 // f(w0..w3) of a 16-entry truth table, bit-sliced: OR over the patterns p with
 // table bit p of the minterm (w_k or ~w_k by bit k of p)

@@ -17,26 +17,9 @@
 #include <hip/hip_runtime.h>
 
 #include "qdec_internal.h"
+#include "qdec_wave_bits.h"
 
 namespace qdec {
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]);
-        const uint32_t lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]);
-        const uint32_t lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0;
-        const uint32_t n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = lo1;
-        c[2] = n2;
-        c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
 
 // dst[e] ^= Bernoulli(thr) for e < count, event `ev`; lanes split the words.
 __device__ __forceinline__ void bern_xor(uint8_t* dst, int count, uint32_t thr, uint32_t ev, int64_t shot,

@@ -10,7 +10,8 @@ parameters (``kind``, ``p``, ``pm``) so the on-device sampler
 (csrc/qdec_sample.hip) can reproduce the noise without a circuit simulator:
 under ``depolarizing_noise`` every data qubit gets DEPOLARIZE1(p) at the start
 of each timestep holding a measurement, and every measurement flips with
-probability pm.
+probability pm.  Every other kind is sampled from the rewritten circuit by the
+Pauli-frame kernel (csrc/qdec_frame.hip).
 """
 from __future__ import annotations
 
@@ -102,9 +103,11 @@ def trivial_noise() -> NoiseRewriter:
 
 
 def circuit_noise(p: float, pm: float | None = None) -> NoiseRewriter:
-    """Gate-level noise (noise_model.py:125-151).  The circuit rewrite is provided;
-    the device sampler does not implement this model (it depends on the gate
-    schedule), so storage sampling with it raises NotImplementedError."""
+    """Gate-level noise (noise_model.py:125-151): DEPOLARIZE2(p) on every gate pair
+    and DEPOLARIZE1(p) on every idle qubit of every tick, measurements flipped
+    with probability pm.  Its effect depends on the gate schedule, so the device
+    samples the rewritten circuit itself (storage_sim.StorageSim.compiled,
+    csrc/qdec_frame.hip)."""
     if pm is None:
         pm = p
 

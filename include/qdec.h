@@ -185,6 +185,73 @@ int qd_sample_faults_device(qd_graph* g, uint32_t seed, uint32_t stream_id, int6
  * qd_graph_set_priors. */
 int qd_graph_sample_tables_copy(const qd_graph* g, uint32_t* thr, int32_t* crow);
 
+/* Pauli-frame sampling of a compiled circuit: replaces Stim's
+ * compile_sampler().sample / compile_detector_sampler().sample (_experiment.py:
+ * 193-197) for circuits of the storage experiment's gate set under any noise
+ * rewriter (noise_model.py:117-151).  A circuit is not a graph and has a handle
+ * of its own.  The program (built by exp_ldpc_amd/circuit.py):
+ *   ops      int32 [n_ops][4]: opcode, first target, target count, 0.  Opcodes:
+ *            0 H, 1 CX, 2 CZ, 3 R, 4 RX, 5 M, 6 MX, 7 X_ERROR, 8 Y_ERROR,
+ *            9 Z_ERROR, 10 DEPOLARIZE1, 11 DEPOLARIZE2 (CX, CZ, DEPOLARIZE2:
+ *            targets in pairs).  MR / MRX are an M / MX followed by an R / RX.
+ *   targets  int32 [n_targets]: qubit indices; a measurement target with bit 30
+ *            set has its record inverted (a reference sample of 1)
+ *   probs    double [n_ops]: the probability of a noise instruction, the record
+ *            flip probability of a measurement, 0 otherwise; converted to u32
+ *            thresholds as in qd_sample_faults_device
+ *   groups   up to 4 output groups; group g has group_rows[g] rows, each the
+ *            parity of a set of measurement records: one CSR over absolute
+ *            record indices, the groups' rows concatenated (row_ptr[rows + 1],
+ *            rec_idx[row_ptr[rows]]); duplicates in a row cancel mod 2
+ * The targets of one H / CX / CZ / R / RX / M / MX instruction are applied in
+ * parallel and must be pairwise disjoint (the compiler splits Stim's in-order
+ * target lists into such groups).  The number of measurements M is the total
+ * target count of the M / MX instructions, record i being the i-th such target.
+ * Create validates every index and refuses a bad program: -71 malformed arrays
+ * (sizes, opcode, target range, odd pair count, CSR bounds), -72 qubit index out
+ * of range, -73 record reference outside [0, M), -74 a qubit twice in one
+ * parallel group, -75 probability outside [0, 1], -76 the circuit needs more
+ * than 160 KiB of LDS (16 B per qubit + 8 B per measurement), -15 device
+ * ordinal.  qd_circuit_create_host validates only and makes no HIP call.
+ * qd_circuit_info: out[10] = qubits, measurements, rows of groups 0..3, LDS
+ * bytes, instructions, Bernoulli / Pauli draw sites, randomisation sites. */
+typedef struct qd_circuit qd_circuit;
+int qd_circuit_create(int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
+                      const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
+                      const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out);
+int qd_circuit_create_host(int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
+                           const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
+                           const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out);
+int qd_circuit_destroy(qd_circuit* c);
+int qd_circuit_info(const qd_circuit* c, int64_t out[10]);
+/* B shots, global indices shot0 .. shot0 + B, enqueued on `stream`.  outs[g]:
+ * group g's rows, u8 [B][rows_g], or with QD_INPUT_PACKED in flags u64
+ * [B][ceil(rows_g / 64)] (the decode's packed layout, padding bits written 0,
+ * 8-B aligned); NULL skips the group.  Frame rules (Stim's frame simulator, bits
+ * (x, z) per qubit and shot): H swaps x and z; CX c t: x_t ^= x_c, z_c ^= z_t;
+ * CZ a b: z_a ^= x_b, z_b ^= x_a; M q: record = x_q ^ flip (^ invert), then
+ * z_q ^= a random bit; MX q: record = z_q ^ flip, then x_q ^= a random bit;
+ * R q: x_q = 0, z_q = a random bit; RX q: z_q = 0, x_q = a random bit; qubits
+ * start with x = z = 0.  The record is the flip against the noiseless reference
+ * sample, taken as all zero unless a target's invert bit says otherwise.
+ * Draws, Philox4x32-10 keyed (seed, stream_id):
+ *   Bernoulli / Pauli site s, shot g: u = lane s % 4 of the block with counter
+ *     (s / 4, 0, g_lo, g_hi); the site fires when u < T.  DEPOLARIZE1 applies
+ *     Pauli 1 + floor(3 u / T) (1 X, 2 Y, 3 Z); DEPOLARIZE2 draws code 1 +
+ *     floor(15 u / T) and applies Pauli code >> 2 to the pair's first qubit and
+ *     code & 3 to its second (0 I).  Sites number the targets (pairs for
+ *     DEPOLARIZE2) of the noise and measurement instructions in program order,
+ *     each instruction starting at the next multiple of 4.
+ *   randomisation site r, shot g: bit g % 32 of lane (g / 32) % 4 of the block
+ *     with counter (r, 1, (g / 128)_lo, (g / 128)_hi); sites number the targets
+ *     of R, RX, M, MX in program order.
+ * Results therefore do not depend on shot0, on how shots are split across
+ * calls, streams or devices, or on alignment.  B = 0 returns 0 and writes
+ * nothing.  Errors: -77 B < 0, unknown flags or a buffer for a group the circuit
+ * lacks, -78 packed buffer not 8-B aligned, -79 host-only circuit. */
+int qd_circuit_sample_device(qd_circuit* c, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
+                             int32_t flags, void* const outs[4], void* stream);
+
 /* Ordered-statistics decoding of shots BP did not converge on (the OSD stage of
  * ldpc v1 bposd_decoder; reference _experiment.py:23-27, 37-40, 77, 96-100).  Host
  * buffers; runs on the host cores (nthreads <= 0: all).  method: 0 = osd0,
