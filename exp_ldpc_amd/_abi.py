@@ -79,6 +79,9 @@ SIGNATURES = {
     "qd_circuit_destroy": (_i32, [_p]),
     "qd_circuit_info": (_i32, [_p, _p]),
     "qd_circuit_sample_device": (_i32, [_p, _u32, _u32, _i64, _i64, _i32, _p, _p]),
+    "qd_circuit_fault_info": (_i32, [_p, _p]),
+    "qd_circuit_fault_table": (_i32, [_p, _i32, _p, _p, _p]),
+    "qd_circuit_faults_device": (_i32, [_p, _i32, _i64, _i64, _i32, _p, _p]),
     "qd_count_flags_device": (_i32, [_p, _i64, C.c_uint8, _p, _p]),
     "qd_osd_batch": (_i32, [_i32, _i32, _p, _p, _i32, _i32, _i64, _p, _p, _p, _p, _i32]),
     "qd_osd_last_error": (C.c_char_p, []),

@@ -400,6 +400,57 @@ class CompiledCircuit:
                    "qd_circuit_sample_device")
         return res
 
+    # ---- elementary faults (include/qdec.h, "Fault propagation"; composed into a DEM by dem.py)
+    def fault_table(self, kind: int = 0):
+        """The library's table of the circuit's elementary faults of one kind
+        (0 noise, 1 gauge), from a host-only handle: int32 arrays (instruction
+        index, index into ``targets``, component: 1 x, 2 z, 3 both, 4 a record flip)."""
+        from . import _abi
+        lib = _abi.load()
+        h = self._create(None)
+        try:
+            if kind not in (0, 1):
+                raise ValueError("fault kind must be 0 (noise) or 1 (gauge)")
+            n = handle_fault_info(h)[kind]
+            op, tgt, comp = (np.zeros(n, np.int32) for _ in range(3))
+            _abi.check(lib.qd_circuit_fault_table(h, int(kind), _abi.ptr(op), _abi.ptr(tgt), _abi.ptr(comp)),
+                       "qd_circuit_fault_table")
+            return op, tgt, comp
+        finally:
+            destroy_handle(h)
+
+    def fault_symptoms_device(self, kind: int = 0, f0: int = 0, F: Optional[int] = None, packed: bool = True,
+                              outputs: Optional[Sequence[str]] = None, device: int = 0, stream=None) -> dict:
+        """Propagate faults f0 .. f0 + F of one kind (default: all from f0) through
+        the circuit on `device` (qd_circuit_faults_device).  Returns {group name:
+        tensor} like sample_device, row f the symptom of fault f0 + f alone."""
+        import torch
+        from . import _abi
+        if F is None:
+            if kind not in (0, 1):
+                raise ValueError("fault kind must be 0 (noise) or 1 (gauge)")
+            F = handle_fault_info(self.handle(device))[kind] - int(f0)
+        names = list(self.groups) if outputs is None else list(outputs)
+        for nme in names:
+            if nme not in self.groups:
+                raise KeyError(f"no output group {nme!r}; the program has {list(self.groups)}")
+        dev = torch.device("cuda", device)
+        res, ptrs = {}, (C.c_void_p * MAX_GROUPS)()
+        for g, (nme, mat) in enumerate(self.groups.items()):
+            if nme not in names:
+                continue
+            rows = mat.shape[0]
+            t = torch.empty((max(F, 0), (rows + 63) // 64) if packed else (max(F, 0), rows),
+                            dtype=torch.int64 if packed else torch.uint8, device=dev)
+            res[nme] = t
+            ptrs[g] = t.data_ptr() if t.numel() else None
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _abi.check(_abi.load().qd_circuit_faults_device(self.handle(device), int(kind), int(f0), int(F),
+                                                        _abi.QD_INPUT_PACKED if packed else 0,
+                                                        C.cast(ptrs, C.c_void_p), C.c_void_p(s)),
+                   "qd_circuit_faults_device")
+        return res
+
 
 # ---- the raw ABI (tests hand qd_circuit_create_host broken programs through these)
 def create_handle(num_qubits, ops, targets, probs, group_rows, row_ptr, rec_idx, device: Optional[int] = None):
@@ -432,6 +483,14 @@ def handle_info(h) -> dict:
     _abi.check(_abi.load().qd_circuit_info(h, _abi.ptr(out)), "qd_circuit_info")
     return {"qubits": int(out[0]), "measurements": int(out[1]), "group_rows": [int(v) for v in out[2:6]],
             "lds_bytes": int(out[6]), "instructions": int(out[7]), "sites": int(out[8]), "rand_sites": int(out[9])}
+
+
+def handle_fault_info(h) -> Tuple[int, int]:
+    """(noise faults, gauge faults) of a handle (qd_circuit_fault_info)."""
+    from . import _abi
+    out = np.zeros(4, np.int64)
+    _abi.check(_abi.load().qd_circuit_fault_info(h, _abi.ptr(out)), "qd_circuit_fault_info")
+    return int(out[0]), int(out[1])
 
 
 def destroy_handle(h) -> None:

@@ -1260,4 +1260,45 @@ int qd_circuit_sample_device(qd_circuit* C, uint32_t seed, uint32_t stream_id, i
     });
 }
 
+int qd_circuit_fault_info(const qd_circuit* C, int64_t out[4]) {
+    return guarded([&] {
+        if (!C || !out) throw Fail(-71, "circuit: null handle or output");
+        out[0] = fault_total(C->hc, 0), out[1] = fault_total(C->hc, 1), out[2] = out[3] = 0;
+    });
+}
+
+int qd_circuit_fault_table(const qd_circuit* C, int32_t kind, int32_t* op, int32_t* target, int32_t* comp) {
+    return guarded([&] {
+        if (!C) throw Fail(-71, "circuit: null handle");
+        circuit_fault_table(C->hc, kind, op, target, comp);
+    });
+}
+
+int qd_circuit_faults_device(qd_circuit* C, int32_t kind, int64_t f0, int64_t F, int32_t flags, void* const outs[4],
+                             void* stream) {
+    return guarded([&] {
+        if (!C) throw Fail(-71, "circuit: null handle");
+        if (kind != 0 && kind != 1) throw Fail(-87, "circuit faults: kind must be 0 (noise) or 1 (gauge)");
+        if (f0 < 0 || F < 0) throw Fail(-88, "circuit faults: negative first fault or count");
+        if (F > (int64_t)fault_total(C->hc, kind) - f0)
+            throw Fail(-89, "circuit faults: window beyond the circuit's " +
+                                std::to_string(fault_total(C->hc, kind)) + " faults of this kind");
+        if (flags & ~QD_INPUT_PACKED) throw Fail(-77, "invalid circuit fault arguments: unknown flags");
+        if (C->host_only) throw Fail(-79, "host-only circuit (qd_circuit_create_host): no device to propagate on");
+        if (F == 0) return;
+        if (!outs) throw Fail(-77, "invalid circuit fault arguments: null output list");
+        const bool packed = (flags & QD_INPUT_PACKED) != 0;
+        void* o[kFrameGroups];
+        for (int g = 0; g < kFrameGroups; ++g) {
+            o[g] = outs[g];
+            if (o[g] && g >= C->hc.n_groups) throw Fail(-77, "output buffer for a group the circuit does not have");
+            if (packed && ((uintptr_t)o[g] & 7)) throw Fail(-78, "packed rows must be 8-B aligned");
+        }
+        hip_check(hipSetDevice(C->device), "hipSetDevice");
+        const int rc = launch_frame_faults(C->dc, C->hc.lds_bytes, kind, (int32_t)f0, (int32_t)F, packed, o,
+                                           C->num_cus, (hipStream_t)stream);
+        if (rc != 0) throw Fail(-102, std::string("fault launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
 }  // extern "C"

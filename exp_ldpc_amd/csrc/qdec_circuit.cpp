@@ -22,7 +22,7 @@ void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int3
     c.ops.reserve(n_ops);
     c.targets.assign(targets, targets + n_targets);
     std::vector<int32_t> seen(num_qubits, -1);  // the last op that touched a qubit
-    uint64_t site = 0, rsite = 0, rec = 0;
+    uint64_t site = 0, rsite = 0, rec = 0, fault = 0;
     for (int32_t i = 0; i < n_ops; ++i) {
         const int32_t op = ops[4 * i], off = ops[4 * i + 1], cnt = ops[4 * i + 2];
         const std::string at = " (instruction " + std::to_string(i) + ")";
@@ -51,16 +51,17 @@ void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int3
         FrameOpRec r{};
         r.op = op, r.tgt_off = off, r.tgt_cnt = cnt;
         r.thr = bern_threshold(p);
-        r.site0 = (uint32_t)site, r.rsite0 = (uint32_t)rsite, r.rec0 = (int32_t)rec;
+        r.site0 = (uint32_t)site, r.rsite0 = (uint32_t)rsite, r.rec0 = (int32_t)rec, r.fault0 = (int32_t)fault;
+        fault += (uint64_t)fault_count(op, cnt, 0);
         if (noise || meas) site += ((uint64_t)(op == FO_DEP2 ? cnt / 2 : cnt) + 3) / 4 * 4;
         if (meas || op == FO_R || op == FO_RX) rsite += (uint64_t)cnt;
         if (meas) rec += (uint64_t)cnt;
-        if (site >= (1ull << 31) || rsite >= (1ull << 31) || rec >= (1ull << 28))
-            throw Fail(-71, "circuit: too many draw sites or records");
+        if (site >= (1ull << 31) || rsite >= (1ull << 31) || rec >= (1ull << 28) || fault >= (1ull << 30))
+            throw Fail(-71, "circuit: too many draw sites, records or faults");
         c.ops.push_back(r);
     }
     c.M = (int32_t)rec;
-    c.n_sites = (uint32_t)site, c.n_rsites = (uint32_t)rsite;
+    c.n_sites = (uint32_t)site, c.n_rsites = (uint32_t)rsite, c.n_faults = (int32_t)fault;
     c.lds_bytes = 16 * (size_t)c.Q + 8 * (size_t)c.M;
     // output groups: rows of record parities
     c.n_groups = n_groups;
@@ -92,6 +93,21 @@ void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int3
     if (c.lds_bytes > kFrameLdsLimit)
         throw Fail(-76, "circuit: " + std::to_string(c.lds_bytes) + " B of LDS (16 B per qubit, 8 B per measurement) "
                             "exceed the kernel's " + std::to_string(kFrameLdsLimit));
+}
+
+void circuit_fault_table(const HostCircuit& c, int kind, int32_t* op, int32_t* target, int32_t* comp) {
+    if (kind != 0 && kind != 1) throw Fail(-87, "circuit faults: kind must be 0 (noise) or 1 (gauge)");
+    if (fault_total(c, kind) && (!op || !target || !comp)) throw Fail(-71, "circuit: null fault table array");
+    int64_t f = 0;
+    for (size_t i = 0; i < c.ops.size(); ++i) {
+        const FrameOpRec& r = c.ops[i];
+        const int32_t cnt = fault_count(r.op, r.tgt_cnt, kind);
+        for (int32_t j = 0; j < cnt; ++j, ++f) {
+            op[f] = (int32_t)i;
+            target[f] = r.tgt_off + fault_target(r.op, j, kind);
+            comp[f] = fault_comp(r.op, j, kind);
+        }
+    }
 }
 
 }  // namespace qdec

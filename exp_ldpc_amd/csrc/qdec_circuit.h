@@ -21,12 +21,39 @@ constexpr int32_t kFrameQubitMask = kFrameInvert - 1;
 
 // One instruction as the kernel reads it.  site0: its first Bernoulli / Pauli
 // draw site (a multiple of 4: one Philox block serves four sites); rsite0: its
-// first randomisation site; rec0: the record index of its first target.
+// first randomisation site, which is also its first gauge fault; rec0: the record
+// index of its first target; fault0: its first noise fault (fault_count below).
 struct FrameOpRec {
     int32_t op, tgt_off, tgt_cnt;
     uint32_t thr, site0, rsite0;
-    int32_t rec0, pad;
+    int32_t rec0, fault0;
 };
+
+// Elementary faults of one instruction with cnt targets (include/qdec.h): noise
+// faults (kind 0) of X/Y/Z_ERROR and M / MX one per target, of DEPOLARIZE1 / 2 an
+// X and a Z per target; gauge faults (kind 1) one per target of R, RX, M, MX.
+constexpr int32_t fault_count(int32_t op, int32_t cnt, int kind) {
+    return kind ? (op == FO_R || op == FO_RX || op == FO_M || op == FO_MX ? cnt : 0)
+           : op == FO_DEP1 || op == FO_DEP2                 ? 2 * cnt
+           : op == FO_M || op == FO_MX || op >= FO_XERR     ? cnt
+                                                            : 0;
+}
+// components of a fault (qd_circuit_fault_table)
+enum FaultComp : int32_t { FC_X = 1, FC_Z = 2, FC_Y = 3, FC_REC = 4 };
+// The component of fault j of an instruction: DEPOLARIZE1 / 2 alternate X, Z along
+// the target list; a gauge fault is the component the sampler randomises there.
+constexpr int32_t fault_comp(int32_t op, int32_t j, int kind) {
+    return kind ? (op == FO_RX || op == FO_MX ? FC_X : FC_Z)
+           : op == FO_M || op == FO_MX         ? FC_REC
+           : op == FO_XERR                     ? FC_X
+           : op == FO_ZERR                     ? FC_Z
+           : op == FO_YERR                     ? FC_Y
+                                               : ((j & 1) ? FC_Z : FC_X);
+}
+// ... and the index into the instruction's targets it acts on
+constexpr int32_t fault_target(int32_t op, int32_t j, int kind) {
+    return !kind && (op == FO_DEP1 || op == FO_DEP2) ? j >> 1 : j;
+}
 
 struct HostCircuit {
     int32_t Q = 0, M = 0;
@@ -37,6 +64,7 @@ struct HostCircuit {
     int32_t row_off[kFrameGroups] = {0, 0, 0, 0};  // its first row in row_ptr
     std::vector<int32_t> row_ptr, rec_idx;         // CSR over record indices, groups concatenated
     uint32_t n_sites = 0, n_rsites = 0;
+    int32_t n_faults = 0;                          // noise faults; the gauge faults are n_rsites
     size_t lds_bytes = 0;                          // 16 Q + 8 M
 };
 
@@ -57,6 +85,11 @@ struct DevCircuit {
 void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
                    const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
                    const int32_t* row_ptr, const int32_t* rec_idx);
+
+// The faults of one kind, in their numbering: the instruction, the index into
+// `targets` and the component (FaultComp) of each; arrays of fault_total entries.
+inline int32_t fault_total(const HostCircuit& c, int kind) { return kind ? (int32_t)c.n_rsites : c.n_faults; }
+void circuit_fault_table(const HostCircuit& c, int kind, int32_t* op, int32_t* target, int32_t* comp);
 
 }  // namespace qdec
 #endif

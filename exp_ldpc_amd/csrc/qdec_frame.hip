@@ -1,4 +1,6 @@
-// qdec_frame.hip -- Pauli-frame sampler of a compiled circuit (qd_circuit_sample_device).
+// qdec_frame.hip -- Pauli-frame sampler of a compiled circuit (qd_circuit_sample_device)
+// and its deterministic twin, the propagation of the circuit's elementary faults
+// (qd_circuit_faults_device; frame_fault_kernel below).
 //
 // Stim's frame simulation of the gate set the storage experiment uses (H, CX, CZ,
 // resets and measurements in Z and X, X/Y/Z_ERROR, DEPOLARIZE1/2), bit-sliced:
@@ -71,6 +73,50 @@ __device__ __forceinline__ uint64_t rand_word(uint32_t rsite, uint64_t s0, uint3
 __device__ __forceinline__ bool pauli_x(uint32_t P) { return P == 1u || P == 2u; }
 __device__ __forceinline__ bool pauli_z(uint32_t P) { return P >= 2u; }
 
+// The gate rules on the frame words (one word = 64 shots, or 64 faults)
+__device__ __forceinline__ void frame_h(uint64_t* x, uint64_t* z, int q) {
+    const uint64_t t = x[q];
+    x[q] = z[q];
+    z[q] = t;
+}
+__device__ __forceinline__ void frame_cx(uint64_t* x, uint64_t* z, int a, int b) {
+    x[b] ^= x[a];
+    z[a] ^= z[b];
+}
+__device__ __forceinline__ void frame_cz(uint64_t* x, uint64_t* z, int a, int b) {
+    z[a] ^= x[b];
+    z[b] ^= x[a];
+}
+
+// The output stage: row r of a group = the parity of its records, a word of the
+// wave's 64 shots (faults); `valid` of them, the first being row b0 of the output.
+template <bool PACKED>
+__device__ __forceinline__ void frame_write_outputs(const DevCircuit& c, const uint64_t* rec, const FrameOuts& o,
+                                                    int64_t b0, int valid, int lane) {
+#pragma unroll
+    for (int g = 0; g < kFrameGroups; ++g) {
+        void* const og = o.p[g];
+        if (!og) continue;
+        const int rows = c.rows[g];
+        const int32_t* rp = c.row_ptr + c.row_off[g];
+        const int words = (rows + 63) / 64;
+        for (int j = 0; j < words; ++j) {
+            const int row = 64 * j + lane;
+            uint64_t v = 0ull;  // rows past the end: the padding bits of a packed row, written 0
+            if (row < rows)
+                for (int e = rp[row]; e < rp[row + 1]; ++e) v ^= rec[c.rec_idx[e]];
+            if constexpr (PACKED) {
+                const uint64_t mine = wave_transpose64(v, lane);  // lane s: shot s's word j
+                if (lane < valid) static_cast<uint64_t*>(og)[(b0 + lane) * words + j] = mine;
+            } else {
+                uint8_t* out = static_cast<uint8_t*>(og) + b0 * rows + row;
+                if (row < rows)
+                    for (int s = 0; s < valid; ++s) out[(int64_t)s * rows] = (uint8_t)((v >> s) & 1ull);
+            }
+        }
+    }
+}
+
 template <bool PACKED>
 __global__ __launch_bounds__(64) void frame_sample_kernel(DevCircuit c, uint32_t seed, uint32_t sid, int64_t shot0,
                                                           int64_t B, FrameOuts o) {
@@ -96,26 +142,13 @@ __global__ __launch_bounds__(64) void frame_sample_kernel(DevCircuit c, uint32_t
             const int T = r.tgt_cnt;
             switch (r.op) {
                 case FO_H:
-                    for (int e = lane; e < T; e += 64) {
-                        const int q = tg[e];
-                        const uint64_t t = x[q];
-                        x[q] = z[q];
-                        z[q] = t;
-                    }
+                    for (int e = lane; e < T; e += 64) frame_h(x, z, tg[e]);
                     break;
                 case FO_CX:
-                    for (int e = lane; 2 * e < T; e += 64) {
-                        const int a = tg[2 * e], b = tg[2 * e + 1];
-                        x[b] ^= x[a];
-                        z[a] ^= z[b];
-                    }
+                    for (int e = lane; 2 * e < T; e += 64) frame_cx(x, z, tg[2 * e], tg[2 * e + 1]);
                     break;
                 case FO_CZ:
-                    for (int e = lane; 2 * e < T; e += 64) {
-                        const int a = tg[2 * e], b = tg[2 * e + 1];
-                        z[a] ^= x[b];
-                        z[b] ^= x[a];
-                    }
+                    for (int e = lane; 2 * e < T; e += 64) frame_cz(x, z, tg[2 * e], tg[2 * e + 1]);
                     break;
                 case FO_R:
                 case FO_RX: {
@@ -225,30 +258,98 @@ __global__ __launch_bounds__(64) void frame_sample_kernel(DevCircuit c, uint32_t
             __syncthreads();
         }
 
-        // outputs: row r of a group = the parity of its records, a word of 64 shots
-#pragma unroll
-        for (int g = 0; g < kFrameGroups; ++g) {
-            void* const og = o.p[g];
-            if (!og) continue;
-            const int rows = c.rows[g];
-            const int32_t* rp = c.row_ptr + c.row_off[g];
-            const int words = (rows + 63) / 64;
-            for (int j = 0; j < words; ++j) {
-                const int row = 64 * j + lane;
-                uint64_t v = 0ull;  // rows past the end: the padding bits of a packed row, written 0
-                if (row < rows)
-                    for (int e = rp[row]; e < rp[row + 1]; ++e) v ^= rec[c.rec_idx[e]];
-                if constexpr (PACKED) {
-                    const uint64_t mine = wave_transpose64(v, lane);  // lane s: shot s's word j
-                    if (lane < valid) static_cast<uint64_t*>(og)[(b0 + lane) * words + j] = mine;
-                } else {
-                    uint8_t* out = static_cast<uint8_t*>(og) + b0 * rows + row;
-                    if (row < rows)
-                        for (int s = 0; s < valid; ++s) out[(int64_t)s * rows] = (uint8_t)((v >> s) & 1ull);
+        frame_write_outputs<PACKED>(c, rec, o, b0, valid, lane);
+        __syncthreads();  // the frame is zeroed for the next 64 shots
+    }
+}
+
+// Fault propagation (qd_circuit_faults_device): the sampler's deterministic twin.
+// Bit s of a word is fault f0 + 64 w + s of wave w instead of a shot, nothing is
+// drawn, and the record is the flip the fault causes: a reset clears both
+// components, a measurement copies the measured one (invert bits do not apply to
+// a flip) and kicks nothing.  At instruction i the lanes whose fault belongs to i
+// XOR their own bit into the word the fault names, after the instruction's own
+// work (a record flip follows the measurement, a gauge fault the reset).  Two
+// lanes may name one word (X_ERROR 0 1 0, a qubit in two DEPOLARIZE2 pairs, two
+// gauge faults never): the XOR is an LDS atomic.  Before a wave's first fault the frame is all zero and stays so, so
+// the wave starts at that fault's instruction, found by bisection over the
+// instructions' first-fault indices (non-decreasing; the last instruction whose
+// index is <= the fault holds it); rec is zeroed up front because the skipped
+// measurements do not write their words.
+template <bool PACKED>
+__global__ __launch_bounds__(64) void frame_fault_kernel(DevCircuit c, int kind, int32_t f0, int32_t F, FrameOuts o) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    uint64_t* x = reinterpret_cast<uint64_t*>(smem);  // [Q]
+    uint64_t* z = x + c.Q;                            // [Q]
+    uint64_t* rec = z + c.Q;                          // [M]
+    const int waves = (F + 63) / 64;
+    const unsigned long long bit = 1ull << lane;
+
+    for (int w = blockIdx.x; w < waves; w += gridDim.x) {
+        const int b0 = w * 64;
+        const int valid = F - b0 < 64 ? F - b0 : 64;
+        const int32_t first = f0 + b0;                        // the wave's first fault
+        const int32_t mine = lane < valid ? first + lane : -1;
+        for (int q = lane; q < 2 * c.Q + c.M; q += 64) x[q] = 0ull;  // x, z and rec are one range
+        int lo = 0, hi = c.n_ops - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            const int32_t base = kind ? (int32_t)c.ops[mid].rsite0 : c.ops[mid].fault0;
+            if (base <= first) lo = mid; else hi = mid - 1;
+        }
+        __syncthreads();
+
+        for (int i = lo; i < c.n_ops; ++i) {
+            const FrameOpRec r = c.ops[i];
+            const int32_t* tg = c.targets + r.tgt_off;
+            const int T = r.tgt_cnt;
+            bool wrote = true;  // the instruction's own work wrote words an injection may name
+            switch (r.op) {
+                case FO_H:
+                    for (int e = lane; e < T; e += 64) frame_h(x, z, tg[e]);
+                    break;
+                case FO_CX:
+                    for (int e = lane; 2 * e < T; e += 64) frame_cx(x, z, tg[2 * e], tg[2 * e + 1]);
+                    break;
+                case FO_CZ:
+                    for (int e = lane; 2 * e < T; e += 64) frame_cz(x, z, tg[2 * e], tg[2 * e + 1]);
+                    break;
+                case FO_R:
+                case FO_RX:
+                    for (int e = lane; e < T; e += 64) x[tg[e]] = z[tg[e]] = 0ull;
+                    break;
+                case FO_M:
+                case FO_MX: {
+                    const uint64_t* read = r.op == FO_M ? x : z;
+                    for (int e = lane; e < T; e += 64) rec[r.rec0 + e] = read[tg[e] & kFrameQubitMask];
+                    break;
+                }
+                default:
+                    wrote = false;
+                    break;
+            }
+            const int32_t base = kind ? (int32_t)r.rsite0 : r.fault0;
+            const int32_t cnt = fault_count(r.op, T, kind);
+            if (base < first + valid && base + cnt > first) {  // some lane's fault is here (the same test in every lane)
+                if (wrote) __syncthreads();
+                const int32_t j = mine - base;
+                if (mine >= 0 && j >= 0 && j < cnt) {
+                    const int32_t comp = fault_comp(r.op, j, kind), e = fault_target(r.op, j, kind);
+                    if (comp == FC_REC) {
+                        atomicXor(reinterpret_cast<unsigned long long*>(rec + r.rec0 + e), bit);
+                    } else {
+                        const int q = tg[e] & kFrameQubitMask;
+                        if (comp & FC_X) atomicXor(reinterpret_cast<unsigned long long*>(x + q), bit);
+                        if (comp & FC_Z) atomicXor(reinterpret_cast<unsigned long long*>(z + q), bit);
+                    }
                 }
             }
+            __syncthreads();
         }
-        __syncthreads();  // the frame is zeroed for the next 64 shots
+
+        frame_write_outputs<PACKED>(c, rec, o, (int64_t)b0, valid, lane);
+        __syncthreads();  // the frame is zeroed for the next 64 faults
     }
 }
 
@@ -273,6 +374,28 @@ int launch_frame_sample(const DevCircuit& c, size_t lds, uint32_t seed, uint32_t
     else
         hipLaunchKernelGGL(frame_sample_kernel<false>, dim3((unsigned)grid), dim3(64), lds, stream, c, seed,
                            stream_id, shot0, B, o);
+    return (int)hipGetLastError();
+}
+
+int launch_frame_faults(const DevCircuit& c, size_t lds, int kind, int32_t f0, int32_t F, bool packed,
+                        void* const outs[kFrameGroups], int num_cus, hipStream_t stream) {
+    if (F <= 0) return 0;
+    FrameOuts o;
+    for (int g = 0; g < kFrameGroups; ++g) o.p[g] = outs[g];
+    const void* fn = packed ? reinterpret_cast<const void*>(frame_fault_kernel<true>)
+                            : reinterpret_cast<const void*>(frame_fault_kernel<false>);
+    if (lds < 16) lds = 16;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    int grid = num_cus * 32;  // as the sampler: one wave per block
+    const int waves = (F + 63) / 64;
+    if (grid > waves) grid = waves;
+    if (packed)
+        hipLaunchKernelGGL(frame_fault_kernel<true>, dim3((unsigned)grid), dim3(64), lds, stream, c, kind, f0, F, o);
+    else
+        hipLaunchKernelGGL(frame_fault_kernel<false>, dim3((unsigned)grid), dim3(64), lds, stream, c, kind, f0, F, o);
     return (int)hipGetLastError();
 }
 

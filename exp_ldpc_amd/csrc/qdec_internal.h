@@ -244,6 +244,10 @@ int launch_count_flags(const uint8_t* flags, int64_t B, uint8_t mask, int64_t* o
 // program's HostCircuit::lds_bytes
 int launch_frame_sample(const DevCircuit& c, size_t lds, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
                         bool packed, void* const outs[kFrameGroups], int num_cus, hipStream_t stream);
+// Faults f0 .. f0 + F of one kind (0 noise, 1 gauge) propagated through the
+// circuit (frame_fault_kernel): the same outputs, a fault where the sampler has a shot
+int launch_frame_faults(const DevCircuit& c, size_t lds, int kind, int32_t f0, int32_t F, bool packed,
+                        void* const outs[kFrameGroups], int num_cus, hipStream_t stream);
 
 // ---------------------------------------------------------------- HGP kernel
 // Hypergraph-product codes get their own f64 min-sum BP kernel, generated and

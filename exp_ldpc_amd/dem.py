@@ -26,6 +26,20 @@ This module supplies the two pieces without Stim:
   the spacetime code of ``spacetime_code.py:46-75``.  Agreement of this
   generator with Stim's output is **unpinned** (Stim absent).
 
+* ``detector_error_model`` extracts the DEM of a circuit of the storage gate
+  set (circuit.py) under any noise: the library propagates every elementary
+  fault of the circuit through the Pauli-frame rules on the GPU
+  (``qd_circuit_faults_device``, csrc/qdec_frame.hip) and ``dem_from_symptoms``
+  composes the symptoms into independent mechanisms (``fault_mechanisms``) and
+  merges equal ones.  It covers both sectors and the faults gates spread, which
+  ``storage_experiment_dem`` does not.  Agreement with Stim's own
+  ``circuit.detector_error_model()`` stays **unpinned** (Stim absent): the
+  column order (here: first appearance in program order), Stim's ``^``
+  decompositions (none are made here) and its approximations for probabilities
+  above 1/2 are not reproduced; the symptom sets and the merged probabilities
+  follow Stim's documented convention of independent X, Y, Z (and 15 two-qubit)
+  components per depolarizing channel.
+
 ``sample_dem`` draws detector samples by sampling every fault independently
 from its prior -- for independent fault mechanisms the distribution Stim's
 detector sampler produces.  ``sample_dem_device`` does the same on the GPU
@@ -42,7 +56,8 @@ import numpy as np
 import scipy.sparse as sp
 
 __all__ = ["DemInstruction", "DetectorErrorModel", "parse_dem", "DetectorSpacetimeCode", "storage_experiment_dem",
-           "sample_dem", "sample_dem_device"]
+           "sample_dem", "sample_dem_device", "depolarize1_component", "depolarize2_component", "fault_mechanisms",
+           "dem_from_symptoms", "check_deterministic_symptoms", "detector_error_model"]
 
 
 @dataclass
@@ -77,6 +92,15 @@ class DetectorErrorModel:
     @property
     def num_errors(self) -> int:
         return sum(1 for ins in self.instructions if ins.type == "error")
+
+    def to_text(self) -> str:
+        """DEM text that ``parse_dem`` reads back to the same model."""
+        lines = []
+        for ins in self.instructions:
+            tg = " ".join([f"D{d}" for d in ins.detectors] + [f"L{o}" for o in ins.observables])
+            head = "error(%r)" % float(ins.args[0]) if ins.type == "error" else ins.type
+            lines.append((head + " " + tg).rstrip())
+        return "\n".join(lines) + "\n"
 
 
 _HEAD = re.compile(r"^([a-z_]+)\s*(?:\(([^)]*)\))?\s*(.*)$")
@@ -269,3 +293,178 @@ def sample_dem_device(decoder, shots: int, seed: int = 0, stream_id: int = 0, sh
     with torch.cuda.device(dev):
         decoder.sample_faults_device(seed, stream_id, shot0, B, det, faults, obs, packed=packed)
     return det, faults, obs
+
+
+# ---------------------------------------------------------------- circuit -> DEM
+def depolarize1_component(p: float) -> float:
+    """q1 with: independent X, Y and Z flips of probability q1 each compose to
+    DEPOLARIZE1(p) exactly (Stim's convention): q1 = 1/2 - 1/2 (1 - 4p/3)^(1/2)."""
+    if not 0.0 <= p <= 0.75:
+        raise ValueError(f"DEPOLARIZE1({p!r}) has no independent components: p must lie in [0, 3/4]")
+    return 0.5 - 0.5 * (1.0 - 4.0 * p / 3.0) ** 0.5
+
+
+def depolarize2_component(p: float) -> float:
+    """q2 with: independent flips of the 15 two-qubit Paulis, probability q2 each,
+    compose to DEPOLARIZE2(p) exactly: q2 = 1/2 - 1/2 (1 - 16p/15)^(1/8)."""
+    if not 0.0 <= p <= 0.9375:
+        raise ValueError(f"DEPOLARIZE2({p!r}) has no independent components: p must lie in [0, 15/16]")
+    return 0.5 - 0.5 * (1.0 - 16.0 * p / 15.0) ** 0.125
+
+
+# members of the mechanisms of one DEPOLARIZE1 target (faults X = 0, Z = 1) and of
+# one DEPOLARIZE2 pair (X_a, Z_a, X_b, Z_b = 0 .. 3), -1 padded; Pauli 1 X, 2 Y, 3 Z
+_PAULI = {0: [], 1: [0], 2: [0, 1], 3: [1]}
+_DEP1 = np.array([(_PAULI[P] + [-1] * 4)[:4] for P in (1, 2, 3)], np.int64)
+_DEP2 = np.array([(_PAULI[c >> 2] + [2 + k for k in _PAULI[c & 3]] + [-1] * 4)[:4] for c in range(1, 16)], np.int64)
+
+
+def fault_mechanisms(cc) -> Tuple[np.ndarray, np.ndarray]:
+    """The independent error mechanisms of a CompiledCircuit, in program order:
+    (probabilities float64 [K], members int64 [K, 4]: the elementary noise faults
+    (include/qdec.h numbering) a mechanism fires together, -1 padded).
+    X/Y/Z_ERROR(p) and M(p): one mechanism of probability p per target;
+    DEPOLARIZE1(p): X, Y = {X, Z}, Z per target, q1 each; DEPOLARIZE2(p): the 15
+    non-identity pairs (first qubit's Pauli = code >> 2, second's = code & 3 for
+    code 1 .. 15), q2 each.  Instructions with p = 0 contribute nothing."""
+    from .circuit import OP_DEP1, OP_DEP2, OP_M, OP_MX, OP_XERR
+    probs, members, f = [], [], 0
+    for (op, _, cnt, _), p in zip(np.asarray(cc.ops).reshape(-1, 4).tolist(), np.asarray(cc.probs).tolist()):
+        if op == OP_DEP1:
+            nf, unit, pat = 2 * cnt, 2, _DEP1
+            q = depolarize1_component(p) if p > 0 else 0.0
+        elif op == OP_DEP2:
+            nf, unit, pat = 2 * cnt, 4, _DEP2
+            q = depolarize2_component(p) if p > 0 else 0.0
+        elif op >= OP_XERR or op in (OP_M, OP_MX):
+            nf, unit, pat, q = cnt, 1, np.array([[0, -1, -1, -1]], np.int64), p
+        else:
+            continue
+        if p > 0 and nf:
+            base = f + unit * np.arange(nf // unit, dtype=np.int64)
+            mem = np.where(pat[None] >= 0, base[:, None, None] + pat[None], -1).reshape(-1, 4)
+            members.append(mem)
+            probs.append(np.full(mem.shape[0], q, np.float64))
+        f += nf
+    if not members:
+        return np.zeros(0, np.float64), np.zeros((0, 4), np.int64)
+    return np.concatenate(probs), np.concatenate(members)
+
+
+def _as_words(sym) -> np.ndarray:
+    """Symptom rows as uint64 words: 0/1 rows (uint8 / bool) are packed, int64 /
+    uint64 rows are taken as QD_INPUT_PACKED words."""
+    from .decoder import pack_rows
+    a = np.asarray(sym.cpu().numpy() if hasattr(sym, "cpu") else sym)
+    if a.dtype in (np.int64, np.uint64):
+        return np.ascontiguousarray(a).view(np.uint64).reshape(a.shape[0], -1)
+    if a.shape[1] == 0:
+        return np.zeros((a.shape[0], 0), np.uint64)
+    return pack_rows(a)
+
+
+def _bits_of(words: np.ndarray, nbits: int) -> np.ndarray:
+    from .decoder import unpack_rows
+    return unpack_rows(words, nbits) if words.shape[1] else np.zeros((words.shape[0], nbits), np.uint8)
+
+
+def dem_from_symptoms(cc, det_sym, obs_sym, num_detectors: int | None = None,
+                      num_observables: int | None = None, mechanisms=None) -> DetectorErrorModel:
+    """The DEM of a CompiledCircuit from the symptoms of its elementary noise
+    faults: row f of det_sym / obs_sym = the detectors / observables fault f
+    flips, as 0/1 rows (uint8) or packed words (int64 / uint64; then the counts
+    default to the circuit's own detectors and observables), arrays or tensors.
+    A mechanism's symptom is the XOR of its members' rows (a fault named twice
+    cancels); mechanisms with identical (detectors, observables) merge by
+    p <- p (1 - p') + p' (1 - p), folded in mechanism order; empty symptoms are
+    dropped; columns come in order of first appearance; a column with
+    observables and no detector is kept.  `mechanisms`: (probabilities, members)
+    in place of fault_mechanisms(cc)."""
+    det_in = np.asarray(det_sym.cpu().numpy() if hasattr(det_sym, "cpu") else det_sym)
+    obs_in = np.asarray(obs_sym.cpu().numpy() if hasattr(obs_sym, "cpu") else obs_sym)
+    packed_d, packed_o = det_in.dtype in (np.int64, np.uint64), obs_in.dtype in (np.int64, np.uint64)
+    D = num_detectors if num_detectors is not None else (cc.detectors.shape[0] if packed_d else det_in.shape[1])
+    K = num_observables if num_observables is not None else (cc.observables.shape[0] if packed_o else obs_in.shape[1])
+    wd, wo = _as_words(det_in), _as_words(obs_in)
+    if wd.shape[0] != wo.shape[0] or wd.shape[1] != (D + 63) // 64 or wo.shape[1] != (K + 63) // 64:
+        raise ValueError("symptom rows do not fit the detector / observable counts")
+    probs, members = fault_mechanisms(cc) if mechanisms is None else mechanisms
+    probs, members = np.asarray(probs, np.float64), np.asarray(members, np.int64).reshape(-1, 4)
+    if members.size and members.max() >= wd.shape[0]:
+        raise ValueError(f"{wd.shape[0]} symptom rows for {int(members.max()) + 1} elementary faults")
+    W = np.concatenate([wd, wo], axis=1)
+    S = np.zeros((probs.size, W.shape[1]), np.uint64)
+    for j in range(4):
+        on = members[:, j] >= 0
+        S[on] ^= W[members[on, j]]
+    keep = S.any(axis=1)
+    S, probs = S[keep], probs[keep]
+    out: List[DemInstruction] = []
+    if S.shape[0]:
+        # equal rows by a stable lexicographic sort (np.unique(axis=0) compares rows as byte strings: ~10x slower)
+        by_row = np.lexsort(S.T[::-1])
+        edge = np.concatenate([[True], (S[by_row[1:]] != S[by_row[:-1]]).any(axis=1)])
+        first = by_row[edge]                                 # stable: a group's first row is its earliest mechanism
+        inv = np.empty(S.shape[0], np.int64)
+        inv[by_row] = np.cumsum(edge) - 1
+        rank_of = np.empty(first.size, np.int64)
+        rank_of[np.argsort(first, kind="stable")] = np.arange(first.size)
+        col = rank_of[inv]                                   # column of each mechanism, by first appearance
+        order = np.argsort(col, kind="stable")               # mechanisms by column, in mechanism order within
+        start = np.searchsorted(col[order], np.arange(first.size))
+        size = np.diff(np.append(start, order.size))
+        merged = probs[order[start]].copy()
+        for r in range(1, int(size.max())):                  # the r-th member of every column that has one
+            cols = np.nonzero(size > r)[0]
+            p2 = probs[order[start[cols] + r]]
+            merged[cols] = merged[cols] * (1.0 - p2) + p2 * (1.0 - merged[cols])
+        rows = S[order[start]]
+        dbits, obits = _bits_of(rows[:, :wd.shape[1]], D), _bits_of(rows[:, wd.shape[1]:], K)
+        for c in range(rows.shape[0]):
+            out.append(DemInstruction("error", [float(merged[c])], np.nonzero(dbits[c])[0].tolist(),
+                                      np.nonzero(obits[c])[0].tolist()))
+    out += [DemInstruction("detector", [], [d], []) for d in range(D)]
+    out += [DemInstruction("logical_observable", [], [], [o]) for o in range(K)]
+    return DetectorErrorModel(out)
+
+
+def check_deterministic_symptoms(det_sym, obs_sym, num_detectors: int, num_observables: int) -> None:
+    """From the symptoms of a circuit's gauge faults (kind 1; 0/1 rows or packed
+    words): raise ValueError naming the first detector, else the first
+    observable, that some reset's or measurement's random component flips.  Its
+    parity is random in the noiseless circuit, and a DEM over it would be wrong."""
+    for name, sym, n in (("detector", det_sym, num_detectors), ("observable", obs_sym, num_observables)):
+        w = _as_words(sym)
+        if w.size:
+            hit = np.nonzero(_bits_of(np.bitwise_or.reduce(w, axis=0)[None], n)[0])[0]
+            if hit.size:
+                raise ValueError(f"{name} {int(hit[0])} is not deterministic: a reset's or measurement's random "
+                                 f"component flips it in the noiseless circuit")
+
+
+def detector_error_model(circuit, device: int = 0, check_deterministic: bool = True, detectors=None,
+                         observables=None) -> DetectorErrorModel:
+    """The detector error model of a circuit (text, ParsedCircuit or
+    CompiledCircuit) of the storage gate set: the counterpart of Stim's
+    ``circuit.detector_error_model()`` (reference _experiment.py:174).  Detectors
+    are the circuit's DETECTORs and observables its OBSERVABLE_INCLUDEs unless
+    `detectors` / `observables` give matrices over the measurement records.
+    Every elementary fault is propagated on `device` (qd_circuit_faults_device).
+    check_deterministic: the gauge faults (every reset's and measurement's
+    randomised component) are propagated too, and a detector or observable one of
+    them flips raises ValueError (check_deterministic_symptoms)."""
+    import torch
+    from .circuit import CompiledCircuit, compile_circuit
+    cc = circuit if isinstance(circuit, CompiledCircuit) else compile_circuit(circuit)
+    prog = cc.with_groups({"detectors": cc.detectors if detectors is None else detectors,
+                           "observables": cc.observables if observables is None else observables})
+    D, K = prog.groups["detectors"].shape[0], prog.groups["observables"].shape[0]
+    try:
+        with torch.cuda.device(device):
+            if check_deterministic:
+                g = prog.fault_symptoms_device(kind=1, device=device)
+                check_deterministic_symptoms(g["detectors"], g["observables"], D, K)
+            s = prog.fault_symptoms_device(kind=0, device=device)
+            return dem_from_symptoms(prog, s["detectors"], s["observables"], D, K)
+    finally:
+        prog.close()

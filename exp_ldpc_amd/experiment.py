@@ -13,8 +13,14 @@ device.  Decoder modes (``--decoder_mode``):
   bpssf_hybrid       BP on spacetime, fold, then BP+SSF on H     (build-defined)
   bp                 BP only on the spacetime matrix
   bpd_detector       BP on the fault check matrix of a detector error model
-                     (_experiment.py:128-151); the storage experiment's DEM is
-                     written by dem.storage_experiment_dem (any R)
+                     (_experiment.py:128-151).  Under depolarizing_noise the
+                     storage experiment's Z-sector DEM is written by
+                     dem.storage_experiment_dem (any R); under every other
+                     rewriter, or with dem_source="circuit", the DEM is
+                     extracted from the noisy circuit itself
+                     (dem.detector_error_model: both sectors, faults spread
+                     through the gates) and the circuit's own detectors are
+                     sampled and decoded
 
 A detector error model of the user's own (any noise model, Stim's DEM text) is
 sampled on the device from its fault probabilities and decoded in batches by
@@ -159,9 +165,14 @@ class BatchPipeline:
 
     def __init__(self, code, rounds: int, mode: str, bp_osd_options: Dict, priors: Tuple[float, float], *,
                  device: int = 0, precision: str = "f64", use_x_logicals: bool = False, osd_threads: int = 0,
-                 noise=None):
+                 noise=None, dem_source: str | None = None, sim=None):
         if mode not in DECODER_MODES:
             raise RuntimeError("Unknown decoder operation mode")
+        if dem_source not in (None, "circuit"):
+            raise ValueError('dem_source is None (by noise model) or "circuit"')
+        if dem_source is not None and mode != "bpd_detector":
+            raise ValueError("dem_source applies to bpd_detector only")
+        self.dem_source = None
         if mode == "bpssf" and rounds > 0:
             mode = "bpssf_hybrid"
         self.mode = mode
@@ -213,27 +224,86 @@ class BatchPipeline:
             # faults (the DEM's last n columns) carry fault-map columns Lz[:, j], so
             # the readout placed there reproduces the observables and the fused
             # check any(F (v ^ x)) = any(obs ^ F x) is the reference's failure flag.
-            if noise is None or getattr(noise, "kind", "") != "depolarizing":
-                raise NotImplementedError("bpd_detector builds its DEM for depolarizing_noise(p, pm) only")
-            from .dem import DetectorSpacetimeCode, storage_experiment_dem
-            if R >= 2:
-                import warnings
-                warnings.warn("bpd_detector at rounds >= 2 decodes the storage experiment's Z-sector DEM, not Stim's "
-                              "two-sector circuit DEM the reference uses (_experiment.py:174,186): its LER is not "
-                              "reference-equivalent (unpinned without Stim; dem.storage_experiment_dem)",
-                              RuntimeWarning, stacklevel=2)
-            self.dem = DetectorSpacetimeCode(storage_experiment_dem(self.H, self.L, R, noise.p, noise.pm))
-            fmap = self.dem.fault_map.toarray() % 2
-            self.n_faults = self.dem.fault_priors.size
-            self.det = Decoder(self.dem.fault_check_matrix, self.dem.fault_priors,
-                               logicals=fmap if fmap.shape[0] else None, **common)
+            kind = getattr(noise, "kind", "")
+            if noise is None or (dem_source is None and kind == "trivial"):
+                raise NotImplementedError("bpd_detector needs a noise model with errors to build its DEM from")
+            if dem_source == "circuit" or kind != "depolarizing":
+                self._init_circuit_dem(code, noise, use_x_logicals, common, sim)
+            else:
+                self._init_storage_dem(noise, common)
         # a plain-H decoder for the sampler
         self.sampler_graph = Decoder(self.H, 0.01, device=self.device)
+
+    def _init_storage_dem(self, noise, common):
+        """bpd_detector under depolarizing_noise: the hand-written Z-sector DEM."""
+        from .dem import DetectorSpacetimeCode, storage_experiment_dem
+        R, n = self.R, self.n
+        self.dem_source = "storage"
+        if R >= 2:
+            import warnings
+            warnings.warn("bpd_detector at rounds >= 2 decodes the storage experiment's Z-sector DEM, not Stim's "
+                          "two-sector circuit DEM the reference uses (_experiment.py:174,186): its LER is not "
+                          "reference-equivalent (unpinned without Stim; dem.storage_experiment_dem).  "
+                          'dem_source="circuit" decodes the DEM extracted from the circuit instead',
+                          RuntimeWarning, stacklevel=3)
+        self.dem = DetectorSpacetimeCode(storage_experiment_dem(self.H, self.L, R, noise.p, noise.pm))
+        fmap = self.dem.fault_map.toarray() % 2
+        self.n_faults = self.dem.fault_priors.size
+        self.det = Decoder(self.dem.fault_check_matrix, self.dem.fault_priors,
+                           logicals=fmap if fmap.shape[0] else None, **common)
+
+    def _init_circuit_dem(self, code, noise, use_x_logicals, common, sim=None):
+        """bpd_detector on the DEM of the noisy circuit itself (reference
+        _experiment.py:174,186): every detector of the circuit in the circuit's
+        order, observables L readout.  The decode's fused check reports
+        any(F (r ^ x)) for a fault-length `readout` r, and the failure flag is
+        any(obs ^ F x): F is row-reduced once, and run() sets r = T obs on its
+        pivot columns (T the inverse of F there), so that F r = obs.  `sim`: the
+        StorageSim of the same experiment, whose circuit is then built once."""
+        from types import SimpleNamespace
+        from .dem import DetectorSpacetimeCode, detector_error_model
+        from .gf2 import row_reduce
+        self.dem_source = "circuit"
+        n = self.n
+        if sim is None:
+            sim = build_storage_simulation(self.R, noise, code, use_x_logicals=use_x_logicals)
+        cc = sim.compiled()
+        L = sp.csr_matrix(self.L)
+        k = L.shape[0]
+        on_records = sp.hstack([sp.csr_matrix((k, cc.num_measurements - n), dtype=L.dtype), L]).tocsr()
+        self.dem_model = detector_error_model(cc, device=self.device, detectors=cc.detectors,
+                                              observables=on_records)
+        full = DetectorSpacetimeCode(self.dem_model)
+        Hc = sp.csc_matrix(full.fault_check_matrix)
+        seen = np.diff(Hc.indptr) > 0
+        # a fault no detector sees cannot be decoded: it stays out of the graph
+        self.undetectable_logical_faults = int((~seen).sum())
+        self.dem = SimpleNamespace(fault_check_matrix=sp.csr_matrix(Hc[:, seen]),
+                                   fault_map=sp.csr_matrix(sp.csc_matrix(full.fault_map)[:, seen]),
+                                   fault_priors=full.fault_priors[seen])
+        nf = self.n_faults = int(seen.sum())
+        fmap = np.asarray(self.dem.fault_map.toarray() % 2, dtype=np.uint8).reshape(k, nf)
+        rref, piv = row_reduce(np.concatenate([fmap, np.eye(k, dtype=np.uint8)], axis=1), ncols=nf)
+        if len(piv) < k:
+            raise ValueError(f"the circuit DEM's fault map has rank {len(piv)} < {k} observables: some observable "
+                             f"is flipped by no detectable fault, so no fault vector reproduces it")
+        self._obs_pivots = np.asarray(piv, dtype=np.int64)
+        self._obs_solve = np.ascontiguousarray(rref[:, nf:].astype(np.float32))    # T, row i for pivot i
+        self.det = Decoder(self.dem.fault_check_matrix, self.dem.fault_priors, logicals=fmap if k else None,
+                           **common)
 
     # ----------------------------------------------------------- helpers
     def decoders(self):
         """The BP decoders this pipeline launches (for the timing ring)."""
         return [d for d in (getattr(self, k, None) for k in ("st", "fin", "ss", "det")) if d is not None]
+
+    def sample(self, sim, B: int, seed: int, stream_id: int = 0, shot0: int = 0):
+        """The device tensors run() takes, sampled from `sim` (a StorageSim of the
+        same experiment): the spacetime syndrome and the readout, or on the
+        circuit-DEM path every detector of the circuit and the readout."""
+        if self.dem_source == "circuit":
+            return sim.sample_detectors_device(B, seed, stream_id, shot0, device=self.device)
+        return sim.sample_device(self.sampler_graph, B, seed, stream_id, shot0)
 
     def launches_per_batch(self, dec) -> int:
         """Decode calls `dec` receives per run(): the single-shot decoder runs
@@ -311,6 +381,17 @@ class BatchPipeline:
         elif mode == "bpssf":
             self.fin.decode_device(B, syn=syn, readout=readout, corr=corr, iters=iters, status=status,
                                    ssf_steps=steps, fail=fail)
+        elif mode == "bpd_detector" and self.dem_source == "circuit":
+            # syn: the circuit's detectors (StorageSim.sample_detectors_device)
+            if self.L.shape[0]:
+                L = torch.from_numpy(np.asarray(sp.csr_matrix(self.L).toarray() % 2, dtype=np.float32)).to(dev)
+                obs = torch.remainder(readout.to(torch.float32) @ L.T, 2)               # exact: sums <= n < 2^24
+                T = torch.from_numpy(self._obs_solve).to(dev)
+                v = torch.zeros((B, self.n_faults), **u8)
+                v[:, torch.from_numpy(self._obs_pivots).to(dev)] = torch.remainder(obs @ T.T, 2).to(torch.uint8)
+                self.det.decode_device(B, syn=syn, readout=v, iters=iters, status=status, fail=fail)
+            else:  # no observable: nothing can fail
+                self.det.decode_device(B, syn=syn, iters=iters, status=status)
         elif mode == "bpd_detector":
             v = torch.zeros((B, self.n_faults), **u8)
             v[:, self.n_faults - n:] = readout
@@ -444,23 +525,26 @@ def _steps(checks):
 
 def run_simulation(samples, code, meas_prior, data_prior, noise_model, noise_model_args, bp_osd_options, rounds,
                    decoder_mode, *, seed: int = DEFAULT_SEED, stream_id: int = 0, shot0: int = 0, device: int = 0,
-                   batch: int = 1 << 18, precision: str = "f64", stats: dict | None = None):
+                   batch: int = 1 << 18, precision: str = "f64", stats: dict | None = None,
+                   dem_source: str | None = None):
     """Sample and decode `samples` shots on one GPU; returns a bool ndarray of
     logical-failure flags (reference run_simulation, _experiment.py:154-210,
-    which returns a list of the same flags)."""
+    which returns a list of the same flags).  dem_source="circuit": bpd_detector
+    decodes the DEM extracted from the circuit under any noise model (the
+    default under every rewriter but depolarizing_noise)."""
     torch = _torch()
     x_steps, z_steps = _steps(code.checks)
     sim = build_storage_simulation(rounds, noise_model(**noise_model_args), code, use_x_logicals=False)
     mp = meas_prior(x_steps, z_steps)
     dp = data_prior(x_steps, z_steps)
     pipe = BatchPipeline(code, rounds, decoder_mode, bp_osd_options, (dp, mp), device=device, precision=precision,
-                         noise=noise_model(**noise_model_args))
+                         noise=noise_model(**noise_model_args), dem_source=dem_source, sim=sim)
     out = np.zeros(samples, dtype=bool)
     agg = {"bp_converged": 0, "iters_sum": 0, "ssf_steps_sum": 0}
     with torch.cuda.device(device):
         for start in range(0, samples, batch):
             b = min(batch, samples - start)
-            syn, rd = sim.sample_device(pipe.sampler_graph, b, seed, stream_id, shot0 + start)
+            syn, rd = pipe.sample(sim, b, seed, stream_id, shot0 + start)
             res = pipe.run(syn, rd)
             out[start:start + b] = res.fail
             agg["bp_converged"] += res.bp_converged
@@ -650,7 +734,7 @@ HBM_PEAK_BYTES_S = 8.0e12  # MI355X HBM3E peak (MI355X_MICROARCH.md)
 
 def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_prior, *, gpus: int | None = None,
             devices=None, seed: int = DEFAULT_SEED, batch: int = 1 << 18, precision: str = "f64",
-            checkpoint: str | None = None, **kwargs):
+            checkpoint: str | None = None, dem_source: str | None = None, **kwargs):
     """Sweep the physical error rate (reference p_sweep, misc/p_sweep.py:17-40).
     Shots are sharded over `gpus` devices by index (shard d decodes a
     contiguous shot range); exactly `samples` shots per point.  `devices`
@@ -671,7 +755,10 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
     fingerprint match (code, logicals, rounds, mode, BP/OSD options, precision,
     seed, sample count and the point index, which is the point's Philox stream
     id), since a recomputed point would then be identical.  The reference
-    writes its CSV only at the end (misc/p_sweep.py:78)."""
+    writes its CSV only at the end (misc/p_sweep.py:78).
+
+    dem_source: BatchPipeline's; points decoded on the circuit's own DEM carry
+    dem_sector = "circuit"."""
     import pandas as pd
     torch = _torch()
     done = _load_checkpoint(checkpoint)
@@ -687,8 +774,8 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
         nm_args = noise_model_args(p_ph)
         dp = data_prior(p_ph, x_steps, z_steps)
         mp = meas_prior(p_ph, x_steps, z_steps)
-        fp = _config_fingerprint(code, rounds, mode, bp_osd_options, precision, seed, samples, pi,
-                                 noise=(noise_model, nm_args, dp, mp))
+        fp = _config_fingerprint(code, rounds, mode if dem_source is None else f"{mode}/dem={dem_source}",
+                                 bp_osd_options, precision, seed, samples, pi, noise=(noise_model, nm_args, dp, mp))
         prev = done.get((float(p_ph), fp))
         if prev is not None:
             data.append(prev)
@@ -699,7 +786,7 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
 
         def pipeline(d):
             return BatchPipeline(code, rounds, mode, bp_osd_options, (dp, mp), device=d, precision=precision,
-                                 noise=nm)
+                                 noise=nm, dem_source=dem_source, sim=sim)
         pipes = [pipeline(d) for d in devs]
         per = math.ceil(samples / ndev)
         shards = [(i, i * per, min(samples, (i + 1) * per)) for i in range(ndev)]
@@ -721,7 +808,7 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
             with torch.cuda.device(d):
                 for start in range(lo, hi, batch):
                     b = min(batch, hi - start)
-                    syn, rd = sim.sample_device(pipe.sampler_graph, b, seed, pi, start)
+                    syn, rd = pipe.sample(sim, b, seed, pi, start)
                     res = pipe.run(syn, rd)
                     acc[0] += int(res.fail.sum())
                     acc[1] += res.bp_converged
@@ -749,7 +836,9 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
         point["precision"] = precision
         point["point_index"] = pi
         point["config_fp"] = fp
-        if mode == "bpd_detector" and rounds >= 2:
+        if pipes[0].dem_source == "circuit":
+            point["dem_sector"] = "circuit"          # dem.detector_error_model of the sampled circuit
+        elif mode == "bpd_detector" and rounds >= 2:
             point["dem_sector"] = "z_only_unpinned"  # see BatchPipeline's warning / dem.storage_experiment_dem
         data.append(point)
         if checkpoint:

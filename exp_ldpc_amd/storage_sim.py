@@ -17,7 +17,9 @@ what the decoding path consumes:
   ``compiled()`` its Pauli-frame program (circuit.py) with the output groups
   ``syn`` (the decoded sector's detectors in spacetime order, round t in columns
   t m .. (t + 1) m - 1) and ``readout`` (the last n records), run by
-  csrc/qdec_frame.hip.
+  csrc/qdec_frame.hip.  ``compiled_detectors()`` is the same program with every
+  detector of the circuit (both sectors) for bpd_detector on the circuit's own
+  detector error model (dem.detector_error_model).
 
 Circuit and program are built on first use: the depolarizing / trivial device
 path never pays for a colouring.  X-check outcomes in host records
@@ -70,6 +72,7 @@ class StorageSim:
         self.use_x_logicals = use_x_logicals
         self._targets = None
         self._compiled = None
+        self._compiled_detectors = None
 
     @property
     def circuit(self):
@@ -89,6 +92,15 @@ class StorageSim:
             self._compiled = cc.with_groups(storage_output_groups(cc, mx, mz, self.code.num_qubits, self.rounds,
                                                                   self.use_x_logicals))
         return self._compiled
+
+    def compiled_detectors(self):
+        """The same program with the groups ``detectors`` (every DETECTOR of the
+        circuit, both sectors, in the circuit's order) and ``readout``: what the
+        circuit's own detector error model is decoded from."""
+        if self._compiled_detectors is None:
+            cc = self.compiled()
+            self._compiled_detectors = cc.with_groups({"detectors": cc.detectors, "readout": cc.groups["readout"]})
+        return self._compiled_detectors
 
     # ---- sampler (device) ----
     def check_matrix(self):
@@ -118,6 +130,14 @@ class StorageSim:
             syn, rd = out
         decoder.sample_storage_device(self.rounds, nm.p, nm.pm, seed, stream_id, shot0, B, syn, rd)
         return syn, rd
+
+    def sample_detectors_device(self, B: int, seed: int, stream_id: int = 0, shot0: int = 0, device: int = 0):
+        """Sample B shots of the circuit itself under any noise model
+        (csrc/qdec_frame.hip).  Returns (detectors uint8[B, D], readout
+        uint8[B, n]): every detector of the circuit, in the circuit's order."""
+        res = self.compiled_detectors().sample_device(B, seed, stream_id, shot0, outputs=("detectors", "readout"),
+                                                      device=device)
+        return res["detectors"], res["readout"]
 
     def records_from_samples(self, syn: np.ndarray, readout: np.ndarray) -> np.ndarray:
         """Host measurement records (reference layout) from sampler output:

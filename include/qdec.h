@@ -252,6 +252,42 @@ int qd_circuit_info(const qd_circuit* c, int64_t out[10]);
 int qd_circuit_sample_device(qd_circuit* c, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
                              int32_t flags, void* const outs[4], void* stream);
 
+/* Fault propagation through a compiled circuit: what Stim's
+ * circuit.detector_error_model() (_experiment.py:174) starts from.  The library
+ * derives the circuit's elementary faults from the program; their numbering does
+ * not depend on the probabilities (instructions with p = 0 are numbered too).
+ *   noise faults (kind 0), in program order:
+ *     X_ERROR / Y_ERROR / Z_ERROR: one per target, the named Pauli (Y: x and z);
+ *     DEPOLARIZE1: two per target, fault 2e = X on target e, 2e + 1 = Z;
+ *     DEPOLARIZE2: four per pair: X_a, Z_a, X_b, Z_b;
+ *     M / MX: one per target, a flip of that record (MR(p) is an M(p) then an R).
+ *   gauge faults (kind 1): one per randomisation site in the sampler's site order
+ *     (the targets of R, RX, M, MX, the opening R included); the injected bit is
+ *     the component the sampler randomises there: z after R and M, x after RX
+ *     and MX.
+ * qd_circuit_fault_info: out[4] = noise faults, gauge faults, 0, 0.
+ * qd_circuit_fault_table: per fault of `kind` the instruction index, the index
+ * into `targets` and the component (1 x, 2 z, 3 both, 4 a record flip); arrays
+ * of the kind's fault count.  Both are host-only (no HIP call).
+ * qd_circuit_faults_device: faults f0 .. f0 + F of one kind, enqueued on
+ * `stream`; outs[g] as in qd_circuit_sample_device with a fault where that call
+ * has a shot: u8 [F][rows_g], or with QD_INPUT_PACKED u64 [F][ceil(rows_g / 64)],
+ * padding bits 0.  Row f is the symptom of fault f alone: the record flips it
+ * causes in an otherwise noiseless run.  Frame rules as the sampler's without any
+ * randomisation: qubits start with x = z = 0; R and RX clear both components;
+ * M q: record = x_q, MX q: record = z_q, the other component is left alone; invert
+ * bits do not apply (a flip is not inverted).  A fault is injected after its own
+ * instruction's work: a record flip XORs the record just written, a gauge fault
+ * the component just reset or measured against.  Every argument is checked
+ * before anything is enqueued, in this order: -87 kind outside {0, 1}, -88 f0 < 0
+ * or F < 0, -89 f0 + F beyond the kind's fault count, -77 unknown flags, -79
+ * host-only circuit, -77 a buffer for a group the circuit lacks, -78 packed
+ * buffer not 8-B aligned.  F = 0 returns 0 and writes nothing. */
+int qd_circuit_fault_info(const qd_circuit* c, int64_t out[4]);
+int qd_circuit_fault_table(const qd_circuit* c, int32_t kind, int32_t* op, int32_t* target, int32_t* comp);
+int qd_circuit_faults_device(qd_circuit* c, int32_t kind, int64_t f0, int64_t F, int32_t flags, void* const outs[4],
+                             void* stream);
+
 /* Ordered-statistics decoding of shots BP did not converge on (the OSD stage of
  * ldpc v1 bposd_decoder; reference _experiment.py:23-27, 37-40, 77, 96-100).  Host
  * buffers; runs on the host cores (nthreads <= 0: all).  method: 0 = osd0,

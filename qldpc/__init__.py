@@ -14,6 +14,7 @@ from exp_ldpc_amd.dem import DetectorSpacetimeCode  # noqa: F401
 from exp_ldpc_amd.storage_sim import StorageSim, build_storage_simulation  # noqa: F401
 from exp_ldpc_amd.schedule import edge_color_bipartite, storage_circuit_text  # noqa: F401
 from exp_ldpc_amd.circuit import CompiledCircuit, compile_circuit  # noqa: F401
+from exp_ldpc_amd.dem import detector_error_model  # noqa: F401  (Stim's circuit.detector_error_model())
 from exp_ldpc_amd.hgp import biregular_hgp, random_biregular_graph, remove_short_cycles  # noqa: F401
 from exp_ldpc_amd.lifted import (lifted_product_code_cyclic, lifted_product_code_pgl2,  # noqa: F401
                                  qc_lifted_product_code)

@@ -9,6 +9,9 @@
 // A valid two-qubit program and one broken variant per refusal of
 // qd_circuit_create (include/qdec.h): the arrays are sized exactly, so a read
 // past a bound the validator should have checked first is a sanitizer report.
+// Every program that validates also has its elementary-fault tables built
+// (circuit_fault_table, both kinds) into arrays of exactly the counted size and
+// checked: instruction and target in range, the faults in program order.
 #include <cstdio>
 #include <vector>
 
@@ -25,15 +28,35 @@ struct Program {
     std::vector<int32_t> rows{1}, row_ptr{0, 2}, rec_idx{0, 1};
 };
 
-static int code_of(const Program& p) {
+// 0 when the fault tables of a validated program are consistent with it
+static int walk_faults(const HostCircuit& c) {
+    for (int kind = 0; kind < 2; ++kind) {
+        const int32_t n = fault_total(c, kind);
+        std::vector<int32_t> op(n), tgt(n), comp(n);
+        circuit_fault_table(c, kind, op.data(), tgt.data(), comp.data());
+        for (int32_t f = 0; f < n; ++f) {
+            if (op[f] < 0 || op[f] >= (int32_t)c.ops.size() || (f && op[f] < op[f - 1])) return -1;
+            const FrameOpRec& r = c.ops[op[f]];
+            if (tgt[f] < r.tgt_off || tgt[f] >= r.tgt_off + r.tgt_cnt || comp[f] < FC_X || comp[f] > FC_REC) return -1;
+            if (f < (kind ? (int32_t)r.rsite0 : r.fault0)) return -1;
+        }
+    }
+    return 0;
+}
+
+static int code_of(const Program& p, int* faults = nullptr) {
     HostCircuit c;
     try {
         build_circuit(c, p.Q, (int32_t)p.ops.size() / 4, p.ops.data(), (int32_t)p.targets.size(), p.targets.data(),
                       p.probs.data(), (int32_t)p.rows.size(), p.rows.data(), p.row_ptr.data(), p.rec_idx.data());
+        if (faults) faults[0] = fault_total(c, 0), faults[1] = fault_total(c, 1);
+        if (walk_faults(c) != 0) return -1;
+        int32_t one = 0;
+        circuit_fault_table(c, 2, &one, &one, &one);  // a bad kind is refused before anything is written
+        return -1;
     } catch (const Fail& e) {
-        return e.code;
+        return e.code == -87 ? 0 : e.code;
     }
-    return 0;
 }
 
 int main() {
@@ -45,6 +68,19 @@ int main() {
     };
     Program p;
     expect("valid", p, 0);
+    int faults[2] = {0, 0};
+    code_of(p, faults);  // DEPOLARIZE1 on one target and two noisy measurements; two measurement gauges
+    std::printf("valid_faults %d %d\n", faults[0], faults[1]);
+    bad += faults[0] != 4 || faults[1] != 2;
+    p = Program();  // every fault-carrying opcode: X/Y/Z_ERROR, DEPOLARIZE2, R, RX, MX
+    p.ops = {FO_R, 0, 2, 0, FO_RX, 0, 1, 0, FO_XERR, 0, 2, 0, FO_YERR, 0, 1, 0, FO_ZERR, 1, 1, 0,
+             FO_DEP2, 0, 2, 0, FO_MX, 0, 1, 0, FO_M, 1, 1, 0};
+    p.targets = {0, 1};
+    p.probs = {0.0, 0.0, 0.1, 0.0, 0.2, 0.3, 0.0, 0.5};
+    code_of(p, faults);
+    std::printf("all_fault_ops %d %d %d\n", code_of(p), faults[0], faults[1]);
+    bad += code_of(p) != 0 || faults[0] != 10 || faults[1] != 5;
+    p = Program();
     p = Program(), p.targets[1] = 2;
     expect("qubit_out_of_range", p, -72);
     p = Program(), p.rec_idx[0] = -1;
