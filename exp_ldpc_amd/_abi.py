@@ -76,6 +76,11 @@ SIGNATURES = {
     "qd_graph_sample_tables_copy": (_i32, [_p, _p, _p]),
     "qd_circuit_create": (_i32, [_i32, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p, C.POINTER(_p)]),
     "qd_circuit_create_host": (_i32, [_i32, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p, C.POINTER(_p)]),
+    "qd_circuit_create_placed": (_i32, [_i32, _i32, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p, C.POINTER(_p)]),
+    "qd_circuit_create_host_placed": (_i32, [_i32, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p, C.POINTER(_p)]),
+    "qd_circuit_set_frame_slots": (_i32, [_p, _i64]),
+    "qd_circuit_frame_info": (_i32, [_p, _p]),
+    "qd_circuit_op_flags_copy": (_i32, [_p, _p]),
     "qd_circuit_destroy": (_i32, [_p]),
     "qd_circuit_info": (_i32, [_p, _p]),
     "qd_circuit_sample_device": (_i32, [_p, _u32, _u32, _i64, _i64, _i32, _p, _p]),

@@ -30,7 +30,7 @@ import numpy as np
 import scipy.sparse as sp
 
 __all__ = ["CompiledCircuit", "Instruction", "ParsedCircuit", "compile_circuit", "parse", "bern_threshold",
-           "SUPPORTED", "OPCODES", "INVERT", "MAX_GROUPS", "LDS_LIMIT"]
+           "SUPPORTED", "OPCODES", "INVERT", "MAX_GROUPS", "LDS_LIMIT", "FRAME_PLACEMENTS"]
 
 OP_H, OP_CX, OP_CZ, OP_R, OP_RX, OP_M, OP_MX, OP_XERR, OP_YERR, OP_ZERR, OP_DEP1, OP_DEP2 = range(12)
 OPCODES = {"H": OP_H, "CX": OP_CX, "CZ": OP_CZ, "R": OP_R, "RX": OP_RX, "M": OP_M, "MX": OP_MX,
@@ -39,6 +39,9 @@ OPCODES = {"H": OP_H, "CX": OP_CX, "CZ": OP_CZ, "R": OP_R, "RX": OP_RX, "M": OP_
 INVERT = 1 << 30       # measurement target bit: record inverted
 MAX_GROUPS = 4
 LDS_LIMIT = 160 * 1024
+# where the kernels keep the frame (include/qdec.h QD_FRAME_*): "auto" = LDS when
+# 16 Q + 8 M fits LDS_LIMIT, else a slot per workgroup in device memory
+FRAME_PLACEMENTS = {"lds": 0, "hbm": 1, "auto": 2}
 
 _ALIAS = {"RZ": "R", "MZ": "M", "MRZ": "MR", "CNOT": "CX"}
 _RESETS = ("R", "RX")
@@ -337,22 +340,40 @@ class CompiledCircuit:
                 np.concatenate(idx) if idx else np.zeros(0, np.int32))
 
     # ---- handles
-    def _create(self, device: Optional[int]):
-        return create_handle(self.num_qubits, *self.abi_arrays(), device=device)
+    def _create(self, device: Optional[int], frame: Optional[str] = "auto"):
+        return create_handle(self.num_qubits, *self.abi_arrays(), device=device, frame=frame)
 
-    def validate(self) -> dict:
-        """Run the library's validation without a device (qd_circuit_create_host)
-        and return qd_circuit_info's figures."""
-        h = self._create(None)
+    def validate(self, frame: Optional[str] = "auto") -> dict:
+        """Run the library's validation without a device
+        (qd_circuit_create_host_placed) and return qd_circuit_info's figures."""
+        h = self._create(None, frame)
         try:
             return handle_info(h)
         finally:
             destroy_handle(h)
 
-    def handle(self, device: int = 0):
-        if device not in self._handles:
-            self._handles[device] = self._create(device)
-        return self._handles[device]
+    def frame_info(self, device: Optional[int] = None, frame: Optional[str] = "auto") -> dict:
+        """qd_circuit_frame_info of the (device, frame) handle, or with
+        device=None of a host-only handle made for the call."""
+        if device is not None:
+            return handle_frame_info(self.handle(device, frame))
+        h = self._create(None, frame)
+        try:
+            return handle_frame_info(h)
+        finally:
+            destroy_handle(h)
+
+    def handle(self, device: int = 0, frame: Optional[str] = "auto"):
+        if (device, frame) not in self._handles:
+            self._handles[(device, frame)] = self._create(device, frame)
+        return self._handles[(device, frame)]
+
+    def set_frame_slots(self, slots: int, device: int = 0, frame: Optional[str] = "auto") -> None:
+        """Slots (resident workgroups) of the HBM kernels' launches on this
+        handle; 0 = the default.  Results do not depend on it."""
+        from . import _abi
+        _abi.check(_abi.load().qd_circuit_set_frame_slots(self.handle(device, frame), int(slots)),
+                   "qd_circuit_set_frame_slots")
 
     def close(self):
         for h in self._handles.values():
@@ -368,8 +389,9 @@ class CompiledCircuit:
     # ---- sampling
     def sample_device(self, B: int, seed: int, stream_id: int = 0, shot0: int = 0, packed: bool = False,
                       outputs: Optional[Sequence[str]] = None, device: int = 0, out: Optional[dict] = None,
-                      stream=None) -> dict:
-        """Sample B shots (global indices shot0 .. shot0 + B) on `device`.
+                      stream=None, frame: Optional[str] = "auto") -> dict:
+        """Sample B shots (global indices shot0 .. shot0 + B) on `device`; `frame`
+        places the frame (FRAME_PLACEMENTS; every placement gives the same bits).
         Returns {group name: tensor} for `outputs` (default: every group):
         uint8 [B, rows], or with packed=True int64 [B, ceil(rows / 64)] holding
         the decode's packed u64 words.  `out` supplies the tensors to write."""
@@ -394,7 +416,7 @@ class CompiledCircuit:
             ptrs[g] = t.data_ptr() if t.numel() else None
         s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         lib = _abi.load()
-        _abi.check(lib.qd_circuit_sample_device(self.handle(device), seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF,
+        _abi.check(lib.qd_circuit_sample_device(self.handle(device, frame), seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF,
                                                 int(shot0), int(B), _abi.QD_INPUT_PACKED if packed else 0,
                                                 C.cast(ptrs, C.c_void_p), C.c_void_p(s)),
                    "qd_circuit_sample_device")
@@ -420,7 +442,8 @@ class CompiledCircuit:
             destroy_handle(h)
 
     def fault_symptoms_device(self, kind: int = 0, f0: int = 0, F: Optional[int] = None, packed: bool = True,
-                              outputs: Optional[Sequence[str]] = None, device: int = 0, stream=None) -> dict:
+                              outputs: Optional[Sequence[str]] = None, device: int = 0, stream=None,
+                              frame: Optional[str] = "auto") -> dict:
         """Propagate faults f0 .. f0 + F of one kind (default: all from f0) through
         the circuit on `device` (qd_circuit_faults_device).  Returns {group name:
         tensor} like sample_device, row f the symptom of fault f0 + f alone."""
@@ -429,7 +452,7 @@ class CompiledCircuit:
         if F is None:
             if kind not in (0, 1):
                 raise ValueError("fault kind must be 0 (noise) or 1 (gauge)")
-            F = handle_fault_info(self.handle(device))[kind] - int(f0)
+            F = handle_fault_info(self.handle(device, frame))[kind] - int(f0)
         names = list(self.groups) if outputs is None else list(outputs)
         for nme in names:
             if nme not in self.groups:
@@ -445,7 +468,7 @@ class CompiledCircuit:
             res[nme] = t
             ptrs[g] = t.data_ptr() if t.numel() else None
         s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        _abi.check(_abi.load().qd_circuit_faults_device(self.handle(device), int(kind), int(f0), int(F),
+        _abi.check(_abi.load().qd_circuit_faults_device(self.handle(device, frame), int(kind), int(f0), int(F),
                                                         _abi.QD_INPUT_PACKED if packed else 0,
                                                         C.cast(ptrs, C.c_void_p), C.c_void_p(s)),
                    "qd_circuit_faults_device")
@@ -453,9 +476,11 @@ class CompiledCircuit:
 
 
 # ---- the raw ABI (tests hand qd_circuit_create_host broken programs through these)
-def create_handle(num_qubits, ops, targets, probs, group_rows, row_ptr, rec_idx, device: Optional[int] = None):
+def create_handle(num_qubits, ops, targets, probs, group_rows, row_ptr, rec_idx, device: Optional[int] = None,
+                  frame=None):
     """qd_circuit_create (device ordinal) or qd_circuit_create_host (None);
-    raises _abi.QdecError carrying the library's code."""
+    with `frame` ("lds", "hbm", "auto", or a raw placement number) the _placed
+    entry points.  Raises _abi.QdecError carrying the library's code."""
     from . import _abi
     lib = _abi.load()
     ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 4)
@@ -470,11 +495,36 @@ def create_handle(num_qubits, ops, targets, probs, group_rows, row_ptr, rec_idx,
     h = C.c_void_p()
     args = (int(num_qubits), ops.shape[0], _abi.ptr(ops), targets.size, _abi.ptr(targets), _abi.ptr(probs),
             group_rows.size, _abi.ptr(group_rows), _abi.ptr(row_ptr), _abi.ptr(rec_idx), C.byref(h))
-    if device is None:
+    if frame is not None:
+        place = FRAME_PLACEMENTS[frame] if isinstance(frame, str) else int(frame)
+        if device is None:
+            _abi.check(lib.qd_circuit_create_host_placed(place, *args), "qd_circuit_create_host_placed")
+        else:
+            _abi.check(lib.qd_circuit_create_placed(place, int(device), *args), "qd_circuit_create_placed")
+    elif device is None:
         _abi.check(lib.qd_circuit_create_host(*args), "qd_circuit_create_host")
     else:
         _abi.check(lib.qd_circuit_create(int(device), *args), "qd_circuit_create")
     return h
+
+
+def handle_frame_info(h) -> dict:
+    """qd_circuit_frame_info: the placement in effect, bytes per slot, the slots
+    of the last HBM launch and the scratch bytes held."""
+    from . import _abi
+    out = np.zeros(4, np.int64)
+    _abi.check(_abi.load().qd_circuit_frame_info(h, _abi.ptr(out)), "qd_circuit_frame_info")
+    return {"placement": {v: k for k, v in FRAME_PLACEMENTS.items()}[int(out[0])], "slot_bytes": int(out[1]),
+            "slots": int(out[2]), "scratch_bytes": int(out[3])}
+
+
+def handle_op_flags(h) -> np.ndarray:
+    """int32 [instructions]: 1 where a noise instruction names a qubit more than
+    once (qd_circuit_op_flags_copy)."""
+    from . import _abi
+    out = np.zeros(handle_info(h)["instructions"], np.int32)
+    _abi.check(_abi.load().qd_circuit_op_flags_copy(h, _abi.ptr(out)), "qd_circuit_op_flags_copy")
+    return out
 
 
 def handle_info(h) -> dict:

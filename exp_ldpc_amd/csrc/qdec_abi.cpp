@@ -1166,19 +1166,37 @@ struct qd_circuit {
     int device = 0;
     int num_cus = 0;
     DeviceSink arena;
+    // where the kernels keep the frame: FP_LDS or FP_HBM (FP_AUTO is resolved at create)
+    int32_t placement = FP_LDS;
+    // HBM placement: the handle's slot scratch.  Every launch records fws_ev on its
+    // stream behind the kernel and a launch on another stream waits for it first
+    // (the chain of qd_graph::ws_ev), so two calls never share live slots; the
+    // scratch is freed or regrown only after fws_ev has completed.
+    void* fws = nullptr;
+    size_t fws_bytes = 0;
+    size_t fws_failed = 0;    // smallest request hipMalloc refused (0: none): not asked for again
+    int64_t slots_cfg = 0;    // qd_circuit_set_frame_slots; 0: num_cus * kFrameHbmSlotsPerCu
+    int64_t slots_last = 0;   // slots of the last launch
+    hipEvent_t fws_ev = nullptr;
+    bool fws_ev_live = false;
+    hipStream_t fws_last = nullptr;
 };
 
 namespace {
 
-int create_circuit(bool host_only, int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
-                   int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
-                   const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out) {
+int create_circuit(int32_t placement, bool host_only, int32_t device, int32_t num_qubits, int32_t n_ops,
+                   const int32_t* ops, int32_t n_targets, const int32_t* targets, const double* probs,
+                   int32_t n_groups, const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
+                   qd_circuit** out) {
     return guarded([&] {
         if (!out) throw Fail(-71, "circuit: null output handle");
         *out = nullptr;
+        if (placement != FP_LDS && placement != FP_HBM && placement != FP_AUTO)
+            throw Fail(-96, "circuit: unknown frame placement (0 LDS, 1 HBM, 2 auto)");
         std::unique_ptr<qd_circuit> C(new qd_circuit());
         build_circuit(C->hc, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows, row_ptr,
-                      rec_idx);
+                      rec_idx, placement != FP_LDS);
+        C->placement = placement == FP_AUTO ? (C->hc.lds_bytes > kFrameLdsLimit ? FP_HBM : FP_LDS) : placement;
         C->host_only = host_only;
         const HostCircuit& h = C->hc;
         DevCircuit& d = C->dc;
@@ -1202,6 +1220,49 @@ int create_circuit(bool host_only, int32_t device, int32_t num_qubits, int32_t n
     });
 }
 
+// The slot scratch of an HBM-placed handle for a launch over `words` 64-shot
+// words on `stream`: waits for the handle's last launch when that ran on another
+// stream, grows the scratch when the launch wants more slots than it holds, and
+// on an allocation failure halves the slot count down to one (results do not
+// depend on it) before failing with -97.  Returns the slots to launch with.
+int64_t frame_scratch_acquire(qd_circuit* C, int64_t words, hipStream_t stream) {
+    const size_t slot = C->hc.lds_bytes;
+    int64_t want = C->slots_cfg > 0 ? C->slots_cfg : (int64_t)C->num_cus * kFrameHbmSlotsPerCu;
+    if (want > words) want = words;
+    if (want < 1) want = 1;
+    if (C->fws_ev_live && C->fws_last != stream) hip_check(hipStreamWaitEvent(stream, C->fws_ev, 0), "hipStreamWaitEvent");
+    const int64_t held = (int64_t)(C->fws_bytes / slot);
+    if (want > held && !(held >= 1 && C->fws_failed && (size_t)want * slot >= C->fws_failed)) {
+        if (C->fws_ev_live) hip_check(hipEventSynchronize(C->fws_ev), "hipEventSynchronize");  // slots may be live
+        if (C->fws) hip_check(hipFree(C->fws), "hipFree frame scratch");
+        C->fws = nullptr;
+        C->fws_bytes = 0;
+        for (int64_t n = want;; n = (n + 1) / 2) {
+            const hipError_t e = hipMalloc(&C->fws, (size_t)n * slot);
+            if (e == hipSuccess) {
+                C->fws_bytes = (size_t)n * slot;
+                break;
+            }
+            (void)hipGetLastError();  // clear the sticky error before any launch checks it
+            C->fws = nullptr;
+            if (e != hipErrorOutOfMemory) hip_check(e, "hipMalloc frame scratch");
+            C->fws_failed = C->fws_failed ? std::min(C->fws_failed, (size_t)n * slot) : (size_t)n * slot;
+            if (n == 1)
+                throw Fail(-97, "circuit: no memory for one frame slot of " + std::to_string(slot) + " B");
+        }
+    }
+    const int64_t have = (int64_t)(C->fws_bytes / slot);
+    return want < have ? want : have;
+}
+
+void frame_scratch_release(qd_circuit* C, int64_t slots, hipStream_t stream) {
+    if (!C->fws_ev) hip_check(hipEventCreateWithFlags(&C->fws_ev, hipEventDisableTiming), "hipEventCreate");
+    hip_check(hipEventRecord(C->fws_ev, stream), "hipEventRecord");
+    C->fws_ev_live = true;
+    C->fws_last = stream;
+    C->slots_last = slots;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1209,21 +1270,63 @@ extern "C" {
 int qd_circuit_create(int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
                       const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
                       const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out) {
-    return create_circuit(false, device, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows,
-                          row_ptr, rec_idx, out);
+    return create_circuit(FP_LDS, false, device, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
+                          group_rows, row_ptr, rec_idx, out);
 }
 
 int qd_circuit_create_host(int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
                            const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
                            const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out) {
-    return create_circuit(true, 0, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows, row_ptr,
-                          rec_idx, out);
+    return create_circuit(FP_LDS, true, 0, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows,
+                          row_ptr, rec_idx, out);
+}
+
+int qd_circuit_create_placed(int32_t placement, int32_t device, int32_t num_qubits, int32_t n_ops,
+                             const int32_t* ops, int32_t n_targets, const int32_t* targets, const double* probs,
+                             int32_t n_groups, const int32_t* group_rows, const int32_t* row_ptr,
+                             const int32_t* rec_idx, qd_circuit** out) {
+    return create_circuit(placement, false, device, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
+                          group_rows, row_ptr, rec_idx, out);
+}
+
+int qd_circuit_create_host_placed(int32_t placement, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
+                                  int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
+                                  const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
+                                  qd_circuit** out) {
+    return create_circuit(placement, true, 0, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
+                          group_rows, row_ptr, rec_idx, out);
+}
+
+int qd_circuit_set_frame_slots(qd_circuit* C, int64_t slots) {
+    return guarded([&] {
+        if (!C) throw Fail(-71, "circuit: null handle");
+        if (slots < 0 || slots > (1ll << 20)) throw Fail(-98, "circuit: frame slots must be 0 (default) .. 2^20");
+        C->slots_cfg = slots;
+    });
+}
+
+int qd_circuit_frame_info(const qd_circuit* C, int64_t out[4]) {
+    return guarded([&] {
+        if (!C || !out) throw Fail(-71, "circuit: null handle or output");
+        out[0] = C->placement, out[1] = (int64_t)C->hc.lds_bytes, out[2] = C->slots_last;
+        out[3] = (int64_t)C->fws_bytes;
+    });
+}
+
+int qd_circuit_op_flags_copy(const qd_circuit* C, int32_t* dup) {
+    return guarded([&] {
+        if (!C || (!dup && !C->hc.ops.empty())) throw Fail(-71, "circuit: null handle or output");
+        for (size_t i = 0; i < C->hc.ops.size(); ++i) dup[i] = C->hc.ops[i].dup;
+    });
 }
 
 int qd_circuit_destroy(qd_circuit* C) {
     return guarded([&] {
         if (!C) return;
         if (!C->host_only) (void)hipSetDevice(C->device);
+        if (C->fws_ev_live) (void)hipEventSynchronize(C->fws_ev);  // a launch may still use the slots
+        if (C->fws) (void)hipFree(C->fws);
+        if (C->fws_ev) (void)hipEventDestroy(C->fws_ev);
         delete C;  // its sink frees the uploads
     });
 }
@@ -1254,8 +1357,16 @@ int qd_circuit_sample_device(qd_circuit* C, uint32_t seed, uint32_t stream_id, i
             if (packed && ((uintptr_t)o[g] & 7)) throw Fail(-78, "packed rows must be 8-B aligned");
         }
         hip_check(hipSetDevice(C->device), "hipSetDevice");
-        const int rc = launch_frame_sample(C->dc, C->hc.lds_bytes, seed, stream_id, shot0, B, packed, o, C->num_cus,
-                                           (hipStream_t)stream);
+        int rc;
+        if (C->placement == FP_HBM) {
+            const int64_t slots = frame_scratch_acquire(C, (B + 63) / 64, (hipStream_t)stream);
+            rc = launch_frame_sample_hbm(C->dc, C->fws, C->hc.lds_bytes, slots, seed, stream_id, shot0, B, packed, o,
+                                         (hipStream_t)stream);
+            frame_scratch_release(C, slots, (hipStream_t)stream);
+        } else {
+            rc = launch_frame_sample(C->dc, C->hc.lds_bytes, seed, stream_id, shot0, B, packed, o, C->num_cus,
+                                     (hipStream_t)stream);
+        }
         if (rc != 0) throw Fail(-102, std::string("sampler launch failed: ") + hipGetErrorString((hipError_t)rc));
     });
 }
@@ -1295,8 +1406,16 @@ int qd_circuit_faults_device(qd_circuit* C, int32_t kind, int64_t f0, int64_t F,
             if (packed && ((uintptr_t)o[g] & 7)) throw Fail(-78, "packed rows must be 8-B aligned");
         }
         hip_check(hipSetDevice(C->device), "hipSetDevice");
-        const int rc = launch_frame_faults(C->dc, C->hc.lds_bytes, kind, (int32_t)f0, (int32_t)F, packed, o,
-                                           C->num_cus, (hipStream_t)stream);
+        int rc;
+        if (C->placement == FP_HBM) {
+            const int64_t slots = frame_scratch_acquire(C, (F + 63) / 64, (hipStream_t)stream);
+            rc = launch_frame_faults_hbm(C->dc, C->fws, C->hc.lds_bytes, slots, kind, (int32_t)f0, (int32_t)F, packed,
+                                         o, (hipStream_t)stream);
+            frame_scratch_release(C, slots, (hipStream_t)stream);
+        } else {
+            rc = launch_frame_faults(C->dc, C->hc.lds_bytes, kind, (int32_t)f0, (int32_t)F, packed, o, C->num_cus,
+                                     (hipStream_t)stream);
+        }
         if (rc != 0) throw Fail(-102, std::string("fault launch failed: ") + hipGetErrorString((hipError_t)rc));
     });
 }

@@ -11,7 +11,7 @@ namespace qdec {
 
 void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
                    const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
-                   const int32_t* row_ptr, const int32_t* rec_idx) {
+                   const int32_t* row_ptr, const int32_t* rec_idx, bool beyond_lds) {
     if (num_qubits < 1 || num_qubits > kFrameQubitMask || n_ops < 0 || n_targets < 0 || n_groups < 0 ||
         n_groups > kFrameGroups)
         throw Fail(-71, "circuit: bad sizes (1 <= qubits, 0 <= ops, targets, 0 <= groups <= 4)");
@@ -33,6 +33,7 @@ void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int3
         const bool meas = op == FO_M || op == FO_MX;
         const bool noise = op >= FO_XERR;
         const double p = probs[i];
+        bool dup = false;
         if (noise || meas) {
             if (!(p >= 0.0 && p <= 1.0)) throw Fail(-75, "circuit: probability outside [0, 1]" + at);
         } else if (p != 0.0) {
@@ -42,13 +43,15 @@ void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int3
             const int32_t t = targets[e];
             if (t < 0 || (!meas && (t & kFrameInvert)) || (t & kFrameQubitMask) >= num_qubits)
                 throw Fail(-72, "circuit: qubit index out of range" + at);
-            if (!noise) {  // lanes split these targets: they must be pairwise disjoint
-                const int32_t q = t & kFrameQubitMask;
-                if (seen[q] == i) throw Fail(-74, "circuit: a qubit twice in one parallel group" + at);
-                seen[q] = i;
+            const int32_t q = t & kFrameQubitMask;
+            if (seen[q] == i) {  // lanes split a gate's targets: they must be pairwise disjoint
+                if (!noise) throw Fail(-74, "circuit: a qubit twice in one parallel group" + at);
+                dup = true;      // legal in a noise line; the HBM kernels apply its sites in order
             }
+            seen[q] = i;
         }
         FrameOpRec r{};
+        r.dup = dup;
         r.op = op, r.tgt_off = off, r.tgt_cnt = cnt;
         r.thr = bern_threshold(p);
         r.site0 = (uint32_t)site, r.rsite0 = (uint32_t)rsite, r.rec0 = (int32_t)rec, r.fault0 = (int32_t)fault;
@@ -90,7 +93,7 @@ void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int3
         c.row_ptr.assign(row_ptr, row_ptr + total + 1);
         c.rec_idx.assign(rec_idx, rec_idx + nnz);
     }
-    if (c.lds_bytes > kFrameLdsLimit)
+    if (c.lds_bytes > kFrameLdsLimit && !beyond_lds)
         throw Fail(-76, "circuit: " + std::to_string(c.lds_bytes) + " B of LDS (16 B per qubit, 8 B per measurement) "
                             "exceed the kernel's " + std::to_string(kFrameLdsLimit));
 }

@@ -18,15 +18,20 @@ constexpr int kFrameGroups = 4;                    // output groups of one progr
 constexpr size_t kFrameLdsLimit = 160 * 1024;      // the launch's dynamic LDS
 constexpr int32_t kFrameInvert = 1 << 30;          // measurement target bit: record inverted
 constexpr int32_t kFrameQubitMask = kFrameInvert - 1;
+// where a handle's kernels keep the frame (include/qdec.h QD_FRAME_*)
+enum FramePlacement : int32_t { FP_LDS = 0, FP_HBM = 1, FP_AUTO = 2 };
 
 // One instruction as the kernel reads it.  site0: its first Bernoulli / Pauli
 // draw site (a multiple of 4: one Philox block serves four sites); rsite0: its
 // first randomisation site, which is also its first gauge fault; rec0: the record
-// index of its first target; fault0: its first noise fault (fault_count below).
+// index of its first target; fault0: its first noise fault (fault_count below);
+// dup: 1 when a noise instruction names a qubit more than once (X_ERROR 0 1 0, a
+// qubit in two DEPOLARIZE2 pairs), so two sites of it may name one frame word.
 struct FrameOpRec {
     int32_t op, tgt_off, tgt_cnt;
     uint32_t thr, site0, rsite0;
     int32_t rec0, fault0;
+    int32_t dup;
 };
 
 // Elementary faults of one instruction with cnt targets (include/qdec.h): noise
@@ -82,9 +87,11 @@ struct DevCircuit {
 // Validates every index of a program and derives the records, sites and the
 // LDS need (throws Fail with the ABI's code; include/qdec.h qd_circuit_create).
 // ops: [n_ops][4] = opcode, first target, target count, 0; probs: [n_ops].
+// beyond_lds: a program over kFrameLdsLimit passes (its frame goes to HBM);
+// otherwise it is refused with -76.
 void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
                    const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
-                   const int32_t* row_ptr, const int32_t* rec_idx);
+                   const int32_t* row_ptr, const int32_t* rec_idx, bool beyond_lds = false);
 
 // The faults of one kind, in their numbering: the instruction, the index into
 // `targets` and the component (FaultComp) of each; arrays of fault_total entries.

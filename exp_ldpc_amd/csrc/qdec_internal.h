@@ -248,6 +248,16 @@ int launch_frame_sample(const DevCircuit& c, size_t lds, uint32_t seed, uint32_t
 // circuit (frame_fault_kernel): the same outputs, a fault where the sampler has a shot
 int launch_frame_faults(const DevCircuit& c, size_t lds, int kind, int32_t f0, int32_t F, bool packed,
                         void* const outs[kFrameGroups], int num_cus, hipStream_t stream);
+// The same two with the frame in global memory (qdec_frame_hbm.hip): `scratch`
+// holds `slots` slots of slot_bytes = 16 Q + 8 M each, one per resident workgroup;
+// the grid is min(64-shot words, slots)
+int launch_frame_sample_hbm(const DevCircuit& c, void* scratch, size_t slot_bytes, int64_t slots, uint32_t seed,
+                            uint32_t stream_id, int64_t shot0, int64_t B, bool packed,
+                            void* const outs[kFrameGroups], hipStream_t stream);
+int launch_frame_faults_hbm(const DevCircuit& c, void* scratch, size_t slot_bytes, int64_t slots, int kind,
+                            int32_t f0, int32_t F, bool packed, void* const outs[kFrameGroups], hipStream_t stream);
+// workgroups (slots) per CU of the HBM frame kernels by default (DESIGN §3.4c has the measurement)
+constexpr int kFrameHbmSlotsPerCu = 8;
 
 // ---------------------------------------------------------------- HGP kernel
 // Hypergraph-product codes get their own f64 min-sum BP kernel, generated and

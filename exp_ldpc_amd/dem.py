@@ -442,6 +442,11 @@ def check_deterministic_symptoms(det_sym, obs_sym, num_detectors: int, num_obser
                                  f"component flips it in the noiseless circuit")
 
 
+# the most symptom output one qd_circuit_faults_device call of detector_error_model
+# writes: a circuit of 10^5 - 10^6 faults is propagated in windows of this size
+FAULT_WINDOW_BYTES = 256 << 20
+
+
 def detector_error_model(circuit, device: int = 0, check_deterministic: bool = True, detectors=None,
                          observables=None) -> DetectorErrorModel:
     """The detector error model of a circuit (text, ParsedCircuit or
@@ -449,7 +454,8 @@ def detector_error_model(circuit, device: int = 0, check_deterministic: bool = T
     ``circuit.detector_error_model()`` (reference _experiment.py:174).  Detectors
     are the circuit's DETECTORs and observables its OBSERVABLE_INCLUDEs unless
     `detectors` / `observables` give matrices over the measurement records.
-    Every elementary fault is propagated on `device` (qd_circuit_faults_device).
+    Every elementary fault is propagated on `device` (qd_circuit_faults_device),
+    in windows of at most FAULT_WINDOW_BYTES of symptoms.
     check_deterministic: the gauge faults (every reset's and measurement's
     randomised component) are propagated too, and a detector or observable one of
     them flips raises ValueError (check_deterministic_symptoms)."""
@@ -459,12 +465,26 @@ def detector_error_model(circuit, device: int = 0, check_deterministic: bool = T
     prog = cc.with_groups({"detectors": cc.detectors if detectors is None else detectors,
                            "observables": cc.observables if observables is None else observables})
     D, K = prog.groups["detectors"].shape[0], prog.groups["observables"].shape[0]
+    from .circuit import handle_fault_info
+    row_bytes = 8 * ((D + 63) // 64 + (K + 63) // 64)
+    window = max(64, FAULT_WINDOW_BYTES // max(row_bytes, 1) // 64 * 64)   # whole 64-fault words
+
+    def symptoms(kind, total):
+        """Packed symptom words of every fault of `kind` on the host, propagated a
+        window at a time so that no call asks the device for more than
+        FAULT_WINDOW_BYTES of output."""
+        det, obs = [], []
+        for f0 in range(0, max(total, 1), window):
+            s = prog.fault_symptoms_device(kind=kind, f0=f0, F=min(window, total - f0), device=device)
+            det.append(s["detectors"].cpu().numpy())
+            obs.append(s["observables"].cpu().numpy())
+        return np.concatenate(det), np.concatenate(obs)
+
     try:
         with torch.cuda.device(device):
+            noise, gauge = handle_fault_info(prog.handle(device))
             if check_deterministic:
-                g = prog.fault_symptoms_device(kind=1, device=device)
-                check_deterministic_symptoms(g["detectors"], g["observables"], D, K)
-            s = prog.fault_symptoms_device(kind=0, device=device)
-            return dem_from_symptoms(prog, s["detectors"], s["observables"], D, K)
+                check_deterministic_symptoms(*symptoms(1, gauge), D, K)
+            return dem_from_symptoms(prog, *symptoms(0, noise), D, K)
     finally:
         prog.close()

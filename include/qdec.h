@@ -214,7 +214,38 @@ int qd_graph_sample_tables_copy(const qd_graph* g, uint32_t* thr, int32_t* crow)
  * than 160 KiB of LDS (16 B per qubit + 8 B per measurement), -15 device
  * ordinal.  qd_circuit_create_host validates only and makes no HIP call.
  * qd_circuit_info: out[10] = qubits, measurements, rows of groups 0..3, LDS
- * bytes, instructions, Bernoulli / Pauli draw sites, randomisation sites. */
+ * bytes (16 Q + 8 M under every placement), instructions, Bernoulli / Pauli draw
+ * sites, randomisation sites.
+ *
+ * Frame placement.  The kernels keep the frame (x[Q], z[Q], rec[M], a u64 word
+ * per 64 shots) either in LDS or, per resident workgroup, in a slot of 16 Q + 8 M
+ * bytes of a scratch in device memory the handle owns.  Both placements give the
+ * same bits.  qd_circuit_create_placed / qd_circuit_create_host_placed take the
+ * placement in front of the arguments of qd_circuit_create / _create_host:
+ *   QD_FRAME_LDS   the two entry points above, -76 included
+ *   QD_FRAME_HBM   always the HBM kernels, at any size
+ *   QD_FRAME_AUTO  LDS when 16 Q + 8 M <= 160 KiB, else HBM
+ * Validation and its codes are the same; -96 for any other placement.  The int32
+ * limits hold under every placement (-71): fewer than 2^31 draw sites and
+ * randomisation sites, 2^28 records, 2^30 noise faults.
+ * qd_circuit_set_frame_slots: slots (resident workgroups) of the HBM kernels'
+ * launches; 0 = the default, 8 per compute unit; a launch uses min(slots, 64-shot
+ * words).  -98 for slots < 0 or > 2^20.  Results do not depend on it.
+ * qd_circuit_frame_info: out[4] = the placement in effect (QD_FRAME_LDS or
+ * QD_FRAME_HBM), bytes per slot (16 Q + 8 M), slots of the last HBM launch,
+ * scratch bytes held.
+ * qd_circuit_op_flags_copy: dup[n_ops] = 1 for a noise instruction that names a
+ * qubit more than once (legal: X_ERROR 0 1 0), else 0.  The HBM sampler applies
+ * the sites of such an instruction one after the other, every other noise
+ * instruction 64 sites at a time; site numbers are the same either way.
+ * The scratch is allocated at the first HBM launch and grown when a launch wants
+ * more slots.  When the allocation fails the slot count is halved down to one;
+ * only then the launch fails with -97.  Launches on one handle from different
+ * streams are chained with an event (the second waits for the first), so no two
+ * share live slots. */
+#define QD_FRAME_LDS 0
+#define QD_FRAME_HBM 1
+#define QD_FRAME_AUTO 2
 typedef struct qd_circuit qd_circuit;
 int qd_circuit_create(int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
                       const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
@@ -222,6 +253,17 @@ int qd_circuit_create(int32_t device, int32_t num_qubits, int32_t n_ops, const i
 int qd_circuit_create_host(int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
                            const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
                            const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out);
+int qd_circuit_create_placed(int32_t placement, int32_t device, int32_t num_qubits, int32_t n_ops,
+                             const int32_t* ops, int32_t n_targets, const int32_t* targets, const double* probs,
+                             int32_t n_groups, const int32_t* group_rows, const int32_t* row_ptr,
+                             const int32_t* rec_idx, qd_circuit** out);
+int qd_circuit_create_host_placed(int32_t placement, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
+                                  int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
+                                  const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
+                                  qd_circuit** out);
+int qd_circuit_set_frame_slots(qd_circuit* c, int64_t slots);
+int qd_circuit_frame_info(const qd_circuit* c, int64_t out[4]);
+int qd_circuit_op_flags_copy(const qd_circuit* c, int32_t* dup);
 int qd_circuit_destroy(qd_circuit* c);
 int qd_circuit_info(const qd_circuit* c, int64_t out[10]);
 /* B shots, global indices shot0 .. shot0 + B, enqueued on `stream`.  outs[g]:
@@ -248,7 +290,8 @@ int qd_circuit_info(const qd_circuit* c, int64_t out[10]);
  * Results therefore do not depend on shot0, on how shots are split across
  * calls, streams or devices, or on alignment.  B = 0 returns 0 and writes
  * nothing.  Errors: -77 B < 0, unknown flags or a buffer for a group the circuit
- * lacks, -78 packed buffer not 8-B aligned, -79 host-only circuit. */
+ * lacks, -78 packed buffer not 8-B aligned, -79 host-only circuit, -97 no memory
+ * for one frame slot (HBM placement). */
 int qd_circuit_sample_device(qd_circuit* c, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
                              int32_t flags, void* const outs[4], void* stream);
 
