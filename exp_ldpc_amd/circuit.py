@@ -387,16 +387,12 @@ class CompiledCircuit:
             pass
 
     # ---- sampling
-    def sample_device(self, B: int, seed: int, stream_id: int = 0, shot0: int = 0, packed: bool = False,
-                      outputs: Optional[Sequence[str]] = None, device: int = 0, out: Optional[dict] = None,
-                      stream=None, frame: Optional[str] = "auto") -> dict:
-        """Sample B shots (global indices shot0 .. shot0 + B) on `device`; `frame`
-        places the frame (FRAME_PLACEMENTS; every placement gives the same bits).
-        Returns {group name: tensor} for `outputs` (default: every group):
-        uint8 [B, rows], or with packed=True int64 [B, ceil(rows / 64)] holding
-        the decode's packed u64 words.  `out` supplies the tensors to write."""
+    def _output_tensors(self, n: int, packed: bool, outputs, out: Optional[dict], device: int):
+        """The {group name: tensor} of a sample / fault call and its c_void_p
+        list: n rows per group of `outputs` (default: every group), uint8
+        [n, rows] or with packed int64 [n, ceil(rows / 64)]; tensors of `out`
+        are checked and used instead of new ones."""
         import torch
-        from . import _abi
         names = list(self.groups) if outputs is None else list(outputs)
         for nme in names:
             if nme not in self.groups:
@@ -407,18 +403,30 @@ class CompiledCircuit:
             if nme not in names:
                 continue
             rows = mat.shape[0]
-            shape = (B, (rows + 63) // 64) if packed else (B, rows)
+            shape = (n, (rows + 63) // 64) if packed else (n, rows)
             dt = torch.int64 if packed else torch.uint8
             t = out[nme] if out is not None and nme in out else torch.empty(shape, dtype=dt, device=dev)
             if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
                 raise ValueError(f"output {nme!r} must be a contiguous {dt} tensor of shape {shape}")
             res[nme] = t
             ptrs[g] = t.data_ptr() if t.numel() else None
+        return res, C.cast(ptrs, C.c_void_p), dev
+
+    def sample_device(self, B: int, seed: int, stream_id: int = 0, shot0: int = 0, packed: bool = False,
+                      outputs: Optional[Sequence[str]] = None, device: int = 0, out: Optional[dict] = None,
+                      stream=None, frame: Optional[str] = "auto") -> dict:
+        """Sample B shots (global indices shot0 .. shot0 + B) on `device`; `frame`
+        places the frame (FRAME_PLACEMENTS; every placement gives the same bits).
+        Returns {group name: tensor} for `outputs` (default: every group):
+        uint8 [B, rows], or with packed=True int64 [B, ceil(rows / 64)] holding
+        the decode's packed u64 words.  `out` supplies the tensors to write."""
+        import torch
+        from . import _abi
+        res, ptrs, dev = self._output_tensors(B, packed, outputs, out, device)
         s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        lib = _abi.load()
-        _abi.check(lib.qd_circuit_sample_device(self.handle(device, frame), seed & 0xFFFFFFFF, stream_id & 0xFFFFFFFF,
-                                                int(shot0), int(B), _abi.QD_INPUT_PACKED if packed else 0,
-                                                C.cast(ptrs, C.c_void_p), C.c_void_p(s)),
+        _abi.check(_abi.load().qd_circuit_sample_device(self.handle(device, frame), seed & 0xFFFFFFFF,
+                                                        stream_id & 0xFFFFFFFF, int(shot0), int(B),
+                                                        _abi.QD_INPUT_PACKED if packed else 0, ptrs, C.c_void_p(s)),
                    "qd_circuit_sample_device")
         return res
 
@@ -453,24 +461,10 @@ class CompiledCircuit:
             if kind not in (0, 1):
                 raise ValueError("fault kind must be 0 (noise) or 1 (gauge)")
             F = handle_fault_info(self.handle(device, frame))[kind] - int(f0)
-        names = list(self.groups) if outputs is None else list(outputs)
-        for nme in names:
-            if nme not in self.groups:
-                raise KeyError(f"no output group {nme!r}; the program has {list(self.groups)}")
-        dev = torch.device("cuda", device)
-        res, ptrs = {}, (C.c_void_p * MAX_GROUPS)()
-        for g, (nme, mat) in enumerate(self.groups.items()):
-            if nme not in names:
-                continue
-            rows = mat.shape[0]
-            t = torch.empty((max(F, 0), (rows + 63) // 64) if packed else (max(F, 0), rows),
-                            dtype=torch.int64 if packed else torch.uint8, device=dev)
-            res[nme] = t
-            ptrs[g] = t.data_ptr() if t.numel() else None
+        res, ptrs, dev = self._output_tensors(max(F, 0), packed, outputs, None, device)
         s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         _abi.check(_abi.load().qd_circuit_faults_device(self.handle(device, frame), int(kind), int(f0), int(F),
-                                                        _abi.QD_INPUT_PACKED if packed else 0,
-                                                        C.cast(ptrs, C.c_void_p), C.c_void_p(s)),
+                                                        _abi.QD_INPUT_PACKED if packed else 0, ptrs, C.c_void_p(s)),
                    "qd_circuit_faults_device")
         return res
 

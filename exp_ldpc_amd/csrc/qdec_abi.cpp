@@ -1263,6 +1263,36 @@ void frame_scratch_release(qd_circuit* C, int64_t slots, hipStream_t stream) {
     C->slots_last = slots;
 }
 
+// The output list of a sampler / fault call (`what`) against the handle: -77 for
+// a null list or a group the circuit lacks, -78 for a misaligned packed row.
+// Copies the pointers to o; true when flags ask for packed rows (the callers
+// refuse unknown flags where their own order of checks has it).
+bool frame_outs(const qd_circuit* C, const char* what, int32_t flags, void* const outs[4], void* (&o)[kFrameGroups]) {
+    if (!outs) throw Fail(-77, std::string("invalid circuit ") + what + " arguments: null output list");
+    const bool packed = (flags & QD_INPUT_PACKED) != 0;
+    for (int g = 0; g < kFrameGroups; ++g) {
+        o[g] = outs[g];
+        if (o[g] && g >= C->hc.n_groups) throw Fail(-77, "output buffer for a group the circuit does not have");
+        if (packed && ((uintptr_t)o[g] & 7)) throw Fail(-78, "packed rows must be 8-B aligned");
+    }
+    return packed;
+}
+
+// One launch over `words` 64-shot (64-fault) words on the handle's placement: in
+// HBM between the acquire and the release of its slot scratch.  -102 with the
+// caller's wording (`what`) when launch(place) does not return 0.
+template <class Launch>
+void frame_launch(qd_circuit* C, const char* what, int64_t words, hipStream_t stream, Launch&& launch) {
+    hip_check(hipSetDevice(C->device), "hipSetDevice");
+    const bool hbm = C->placement == FP_HBM;
+    FramePlace at;
+    at.placement = C->placement, at.lds = at.slot_bytes = C->hc.lds_bytes, at.num_cus = C->num_cus;
+    if (hbm) at.slots = frame_scratch_acquire(C, words, stream), at.scratch = C->fws;
+    const int rc = launch(at);
+    if (hbm) frame_scratch_release(C, at.slots, stream);
+    if (rc != 0) throw Fail(-102, std::string(what) + " launch failed: " + hipGetErrorString((hipError_t)rc));
+}
+
 }  // namespace
 
 extern "C" {
@@ -1348,26 +1378,11 @@ int qd_circuit_sample_device(qd_circuit* C, uint32_t seed, uint32_t stream_id, i
         if (C->host_only) throw Fail(-79, "host-only circuit (qd_circuit_create_host): no device to sample on");
         if (B < 0 || (flags & ~QD_INPUT_PACKED)) throw Fail(-77, "invalid circuit sampler arguments");
         if (B == 0) return;
-        if (!outs) throw Fail(-77, "invalid circuit sampler arguments: null output list");
-        const bool packed = (flags & QD_INPUT_PACKED) != 0;
         void* o[kFrameGroups];
-        for (int g = 0; g < kFrameGroups; ++g) {
-            o[g] = outs[g];
-            if (o[g] && g >= C->hc.n_groups) throw Fail(-77, "output buffer for a group the circuit does not have");
-            if (packed && ((uintptr_t)o[g] & 7)) throw Fail(-78, "packed rows must be 8-B aligned");
-        }
-        hip_check(hipSetDevice(C->device), "hipSetDevice");
-        int rc;
-        if (C->placement == FP_HBM) {
-            const int64_t slots = frame_scratch_acquire(C, (B + 63) / 64, (hipStream_t)stream);
-            rc = launch_frame_sample_hbm(C->dc, C->fws, C->hc.lds_bytes, slots, seed, stream_id, shot0, B, packed, o,
-                                         (hipStream_t)stream);
-            frame_scratch_release(C, slots, (hipStream_t)stream);
-        } else {
-            rc = launch_frame_sample(C->dc, C->hc.lds_bytes, seed, stream_id, shot0, B, packed, o, C->num_cus,
-                                     (hipStream_t)stream);
-        }
-        if (rc != 0) throw Fail(-102, std::string("sampler launch failed: ") + hipGetErrorString((hipError_t)rc));
+        const bool packed = frame_outs(C, "sampler", flags, outs, o);
+        frame_launch(C, "sampler", (B + 63) / 64, (hipStream_t)stream, [&](const FramePlace& at) {
+            return launch_frame_sample(C->dc, at, seed, stream_id, shot0, B, packed, o, (hipStream_t)stream);
+        });
     });
 }
 
@@ -1397,26 +1412,11 @@ int qd_circuit_faults_device(qd_circuit* C, int32_t kind, int64_t f0, int64_t F,
         if (flags & ~QD_INPUT_PACKED) throw Fail(-77, "invalid circuit fault arguments: unknown flags");
         if (C->host_only) throw Fail(-79, "host-only circuit (qd_circuit_create_host): no device to propagate on");
         if (F == 0) return;
-        if (!outs) throw Fail(-77, "invalid circuit fault arguments: null output list");
-        const bool packed = (flags & QD_INPUT_PACKED) != 0;
         void* o[kFrameGroups];
-        for (int g = 0; g < kFrameGroups; ++g) {
-            o[g] = outs[g];
-            if (o[g] && g >= C->hc.n_groups) throw Fail(-77, "output buffer for a group the circuit does not have");
-            if (packed && ((uintptr_t)o[g] & 7)) throw Fail(-78, "packed rows must be 8-B aligned");
-        }
-        hip_check(hipSetDevice(C->device), "hipSetDevice");
-        int rc;
-        if (C->placement == FP_HBM) {
-            const int64_t slots = frame_scratch_acquire(C, (F + 63) / 64, (hipStream_t)stream);
-            rc = launch_frame_faults_hbm(C->dc, C->fws, C->hc.lds_bytes, slots, kind, (int32_t)f0, (int32_t)F, packed,
-                                         o, (hipStream_t)stream);
-            frame_scratch_release(C, slots, (hipStream_t)stream);
-        } else {
-            rc = launch_frame_faults(C->dc, C->hc.lds_bytes, kind, (int32_t)f0, (int32_t)F, packed, o, C->num_cus,
-                                     (hipStream_t)stream);
-        }
-        if (rc != 0) throw Fail(-102, std::string("fault launch failed: ") + hipGetErrorString((hipError_t)rc));
+        const bool packed = frame_outs(C, "fault", flags, outs, o);
+        frame_launch(C, "fault", (F + 63) / 64, (hipStream_t)stream, [&](const FramePlace& at) {
+            return launch_frame_faults(C->dc, at, kind, (int32_t)f0, (int32_t)F, packed, o, (hipStream_t)stream);
+        });
     });
 }
 

@@ -239,24 +239,27 @@ int launch_sample_faults(const DevGraph& g, const uint32_t* thr, const int32_t* 
                          uint32_t stream_id, int64_t shot0, int64_t B, bool packed, void* det, void* faults,
                          uint8_t* obs, int num_cus, hipStream_t stream);
 int launch_count_flags(const uint8_t* flags, int64_t B, uint8_t mask, int64_t* out, hipStream_t stream);
-// B shots of a compiled circuit (frame_sample_kernel, qdec_frame.hip): group g's
-// rows to outs[g] (nullable), byte rows or u64 words when packed; lds = the
-// program's HostCircuit::lds_bytes
-int launch_frame_sample(const DevCircuit& c, size_t lds, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
-                        bool packed, void* const outs[kFrameGroups], int num_cus, hipStream_t stream);
+// Where a launch of the frame kernels (qdec_frame.hip) keeps the frame.  FP_LDS:
+// lds = the program's HostCircuit::lds_bytes; the grid is min(64-shot words,
+// 32 num_cus).  FP_HBM: `scratch` holds `slots` slots of slot_bytes = 16 Q + 8 M
+// each, one per resident workgroup; the grid is min(64-shot words, slots).
+struct FramePlace {
+    int32_t placement = FP_LDS;
+    size_t lds = 0;
+    int num_cus = 0;
+    void* scratch = nullptr;
+    size_t slot_bytes = 0;
+    int64_t slots = 0;
+};
+// B shots of a compiled circuit (frame_sample_kernel): group g's rows to outs[g]
+// (nullable), byte rows or u64 words when packed
+int launch_frame_sample(const DevCircuit& c, const FramePlace& at, uint32_t seed, uint32_t stream_id, int64_t shot0,
+                        int64_t B, bool packed, void* const outs[kFrameGroups], hipStream_t stream);
 // Faults f0 .. f0 + F of one kind (0 noise, 1 gauge) propagated through the
 // circuit (frame_fault_kernel): the same outputs, a fault where the sampler has a shot
-int launch_frame_faults(const DevCircuit& c, size_t lds, int kind, int32_t f0, int32_t F, bool packed,
-                        void* const outs[kFrameGroups], int num_cus, hipStream_t stream);
-// The same two with the frame in global memory (qdec_frame_hbm.hip): `scratch`
-// holds `slots` slots of slot_bytes = 16 Q + 8 M each, one per resident workgroup;
-// the grid is min(64-shot words, slots)
-int launch_frame_sample_hbm(const DevCircuit& c, void* scratch, size_t slot_bytes, int64_t slots, uint32_t seed,
-                            uint32_t stream_id, int64_t shot0, int64_t B, bool packed,
-                            void* const outs[kFrameGroups], hipStream_t stream);
-int launch_frame_faults_hbm(const DevCircuit& c, void* scratch, size_t slot_bytes, int64_t slots, int kind,
-                            int32_t f0, int32_t F, bool packed, void* const outs[kFrameGroups], hipStream_t stream);
-// workgroups (slots) per CU of the HBM frame kernels by default (DESIGN §3.4c has the measurement)
+int launch_frame_faults(const DevCircuit& c, const FramePlace& at, int kind, int32_t f0, int32_t F, bool packed,
+                        void* const outs[kFrameGroups], hipStream_t stream);
+// workgroups (slots) per CU of the frame kernels in HBM by default (DESIGN §3.4c has the measurement)
 constexpr int kFrameHbmSlotsPerCu = 8;
 
 // ---------------------------------------------------------------- HGP kernel

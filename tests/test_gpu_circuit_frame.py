@@ -1,4 +1,4 @@
-"""The Pauli frame in HBM (csrc/qdec_frame_hbm.hip; QD_FRAME_HBM / QD_FRAME_AUTO):
+"""The Pauli frame in HBM (FrameInHbm in csrc/qdec_frame.hip; QD_FRAME_HBM / QD_FRAME_AUTO):
 forced onto small circuits it equals the numpy models and the LDS kernels bit for
 bit, and circuits beyond the LDS kernels' 160 KiB -- by one qubit, by
 measurements, and the n = 10^4 storage circuit -- sample, propagate their faults
@@ -206,6 +206,35 @@ def test_generated_circuit_fault_symptoms_in_hbm(gpu_available, code225):
     refs = [fault_model.symptoms(cc, kind) for kind in (0, 1)]
     assert refs[0]["detectors"].any() and refs[0]["observables"].any()
     _faults_equal_everywhere(cc, refs, lambda total: [(0, total), (37, 130), (total - 101, 101)])
+    cc.close()
+
+
+def test_lines_of_257_targets_take_the_gate_helpers_second_step(gpu_available):
+    """514 qubits (10,280 B of frame and records, far inside LDS), every line over
+    257 = 4 * 64 + 1 targets or pairs: with four targets per lane in flight the gate
+    and measurement helpers run one full step and a step in which lane 0 alone holds
+    a target; the noise lines run four 64-site batches and a one-site tail.  The
+    order makes every line matter to the records (dropping any one changes the
+    model's): RX's random x and DEPOLARIZE1 reach z of the odd qubits through CZ,
+    come back to z of the even ones through CX with DEPOLARIZE2's, and H turns
+    that into what M reads.  Shots against frame_model in both placements; all
+    faults of both kinds, and noise faults 615 .. 745 (inside the DEPOLARIZE2
+    line's 514 .. 1542), against fault_model."""
+    from exp_ldpc_amd.circuit import compile_circuit
+    even = " ".join(str(2 * i) for i in range(257))
+    pairs = " ".join(f"{2 * i} {2 * i + 1}" for i in range(257))
+    cc = compile_circuit("\n".join([
+        f"RX {even}", f"DEPOLARIZE1(0.25) {even}", f"CZ {pairs}", f"DEPOLARIZE2(0.3) {pairs}", f"CX {pairs}",
+        f"H {even}", f"M(0.1) {even}", "DETECTOR rec[-1] rec[-257]", "DETECTOR rec[-2] rec[-65] rec[-129]",
+        "OBSERVABLE_INCLUDE(0) rec[-1] rec[-64] rec[-193]"]))
+    assert cc.num_qubits == 514 and cc.num_measurements == 257 and cc.lds_bytes == 16 * 514 + 8 * 257
+    ref = frame_model.sample(cc, SEED, 3, 37, 65)
+    assert ref["detectors"].any() and ref["observables"].any() and 0.05 < ref["records"].mean() < 0.95
+    _both_placements_equal(cc, ref, ("detectors", "observables", "records"), 65, shot0=37)
+    refs = [fault_model.symptoms(cc, kind) for kind in (0, 1)]
+    assert refs[0]["rec"].shape[0] == 514 + 1028 + 257 and fault_model.enumerate_faults(cc.ops, 0)[615][0] == 4
+    assert all(r["detectors"].any() and r["observables"].any() for r in refs)
+    _faults_equal_everywhere(cc, refs, lambda total: [(0, total)] + ([(615, 130)] if total == 1799 else []))
     cc.close()
 
 

@@ -1,5 +1,5 @@
-"""The Pauli frame in HBM (frame_sample_hbm_kernel / frame_fault_hbm_kernel,
-csrc/qdec_frame_hbm.hip) on one MI355X.  Diagnostic companion of bench.py.
+"""The Pauli frame in HBM (frame_sample_kernel / frame_fault_kernel with FrameInHbm,
+csrc/qdec_frame.hip) on one MI355X.  Diagnostic companion of bench.py.
 
 (a) The n = 225, R = 3 circuit_noise circuit, which fits LDS, under the LDS
     placement and under forced HBM placement: the price of the placement.
