@@ -27,6 +27,7 @@ QD_F64, QD_F32 = 0, 1
 QD_SYN_ADD_BASE, QD_SYN_ADD_READOUT = 1, 2
 QD_INPUT_PACKED = 16  # bit-packed input rows (include/qdec.h)
 QD_ST_BP_CONVERGED, QD_ST_SATISFIED = 1, 2
+QD_OSD_ONCHIP, QD_OSD_HBM, QD_OSD_AUTO = 0, 1, 2  # where the device OSD keeps its rows
 
 
 class QdParams(C.Structure):
@@ -99,6 +100,11 @@ SIGNATURES = {
     "qd_osd_device_supported": (_i32, [_p]),
     "qd_osd_kernel_info": (_i32, [_p, _p]),
     "qd_osd_batch_device": (_i32, [_p, _i32, _i32, _i64, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "qd_osd_batch_device_placed": (_i32, [_p, _i32, _i32, _i64, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p,
+                                          _i32]),
+    "qd_osd_kernel_info_placed": (_i32, [_p, _i32, _p]),
+    "qd_osd_set_slots": (_i32, [_p, _i64]),
+    "qd_osd_hbm_info": (_i32, [_p, _p]),
     "qd_graph_set_option": (_i32, [_p, _i32, _i32]),
     "qd_graph_get_option": (_i32, [_p, _i32, C.POINTER(_i32)]),
     "qd_graph_ssf_tables": (_i32, [_p, C.POINTER(_i32), C.POINTER(_i64)]),

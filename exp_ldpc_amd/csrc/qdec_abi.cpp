@@ -123,6 +123,16 @@ struct qd_graph : HostGraph {
     hipEvent_t ssf_done[2] = {nullptr, nullptr};
     bool ssf_done_live[2] = {false, false};
     hipStream_t ws_last = nullptr;
+    // slot scratch of osd_hbm_kernel (grow only; osd_scratch_acquire): one slot per
+    // workgroup, chained over streams through an event of its own
+    void* osd_ws = nullptr;
+    size_t osd_ws_bytes = 0;
+    size_t osd_ws_failed = 0;     // smallest size whose allocation failed (0: none)
+    int64_t osd_slots_cfg = 0;    // qd_osd_set_slots (0: the default)
+    int64_t osd_slots_last = 0;   // slots of the last HBM launch
+    hipEvent_t osd_ev = nullptr;
+    bool osd_ev_live = false;
+    hipStream_t osd_last = nullptr;
     // kernels the last decode on this handle launched (qd_graph_last_kernels)
     std::string last_bp, last_ssf, last_pre;
     // qd_graph_create_host: tables only, no device, no stream; decodes refuse it
@@ -280,6 +290,64 @@ void attach_unpack(qd_graph* G, const DecodePlan& plan, DecodeArgs& a) {
         G->ubuf_bytes = need;
     }
     a.unpack_buf = static_cast<uint8_t*>(G->ubuf);
+}
+
+void check_osd_placement(int32_t placement) {
+    if (placement != QD_OSD_ONCHIP && placement != QD_OSD_HBM && placement != QD_OSD_AUTO)
+        throw Fail(-44, "unknown OSD placement (0 on-chip, 1 HBM, 2 auto)");
+}
+
+// The slot scratch of osd_hbm_kernel for a launch over B shots on `stream`:
+// waits for the handle's last HBM launch when that ran on another stream, grows
+// the scratch when the launch wants more slots than it holds (num_cus *
+// kOsdHbmSlotsPerCu or qd_osd_set_slots, at most B, at most a quarter of the
+// free device memory: -45 when that does not hold one slot), and on an
+// allocation failure halves the slot count down to one (results do not depend
+// on it) before failing with -46.  Returns the slots to launch with.
+int64_t osd_scratch_acquire(qd_graph* G, const OsdHbmLayout& L, int64_t B, hipStream_t stream) {
+    const size_t slot = (size_t)L.slot_bytes;
+    int64_t want = G->osd_slots_cfg > 0 ? G->osd_slots_cfg : (int64_t)G->num_cus * kOsdHbmSlotsPerCu;
+    if (want > B) want = B;
+    if (want < 1) want = 1;
+    if (G->osd_ev_live && G->osd_last != stream) hip_check(hipStreamWaitEvent(stream, G->osd_ev, 0), "hipStreamWaitEvent");
+    int64_t held = (int64_t)(G->osd_ws_bytes / slot);
+    if (want > held && !(held >= 1 && G->osd_ws_failed && (size_t)want * slot >= G->osd_ws_failed)) {
+        size_t free_b = 0, total_b = 0;
+        hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+        const int64_t cap = (int64_t)((free_b + G->osd_ws_bytes) / 4 / slot);  // the scratch held counts as free
+        if (cap < 1)
+            throw Fail(-45, "one OSD slot of " + std::to_string(slot) + " B is beyond the scratch budget (a quarter "
+                            "of the free device memory)");
+        if (want > cap) want = cap;
+    }
+    if (want > held && !(held >= 1 && G->osd_ws_failed && (size_t)want * slot >= G->osd_ws_failed)) {
+        if (G->osd_ev_live) hip_check(hipEventSynchronize(G->osd_ev), "hipEventSynchronize");  // slots may be live
+        if (G->osd_ws) hip_check(hipFree(G->osd_ws), "hipFree OSD scratch");
+        G->osd_ws = nullptr;
+        G->osd_ws_bytes = 0;
+        for (int64_t n = want;; n = (n + 1) / 2) {
+            const hipError_t e = hipMalloc(&G->osd_ws, (size_t)n * slot);
+            if (e == hipSuccess) {
+                G->osd_ws_bytes = (size_t)n * slot;
+                break;
+            }
+            (void)hipGetLastError();  // clear the sticky error before any launch checks it
+            G->osd_ws = nullptr;
+            if (e != hipErrorOutOfMemory) hip_check(e, "hipMalloc OSD scratch");
+            G->osd_ws_failed = G->osd_ws_failed ? std::min(G->osd_ws_failed, (size_t)n * slot) : (size_t)n * slot;
+            if (n == 1) throw Fail(-46, "no memory for one OSD slot of " + std::to_string(slot) + " B");
+        }
+    }
+    held = (int64_t)(G->osd_ws_bytes / slot);
+    return want < held ? want : held;
+}
+
+void osd_scratch_release(qd_graph* G, int64_t slots, hipStream_t stream) {
+    if (!G->osd_ev) hip_check(hipEventCreateWithFlags(&G->osd_ev, hipEventDisableTiming), "hipEventCreate");
+    hip_check(hipEventRecord(G->osd_ev, stream), "hipEventRecord");
+    G->osd_ev_live = true;
+    G->osd_last = stream;
+    G->osd_slots_last = slots;
 }
 
 void note_kernels(qd_graph* G) {
@@ -647,6 +715,9 @@ int qd_graph_destroy(qd_graph* g) {
         if (g->qws) (void)hipFree(g->qws);
         if (g->mws) (void)hipFree(g->mws);
         if (g->ubuf) (void)hipFree(g->ubuf);
+        if (g->osd_ev_live) (void)hipEventSynchronize(g->osd_ev);  // an HBM OSD launch may still use its slots
+        if (g->osd_ev) (void)hipEventDestroy(g->osd_ev);
+        if (g->osd_ws) (void)hipFree(g->osd_ws);
         if (g->cmpc) (void)hipFree(g->cmpc);
         if (g->ctl) (void)hipFree(g->ctl);
         hgp_plan_destroy(g->hgp);
@@ -851,18 +922,34 @@ int qd_osd_batch_device(qd_graph* G, int32_t method, int32_t order, int64_t B, c
                         const void* llr, int32_t llr_precision, const uint8_t* status, const uint8_t* base,
                         const uint8_t* readout, uint8_t* osd0_out, uint8_t* osdw_out, uint8_t* corr_out, uint8_t* fail,
                         void* stream) {
+    return qd_osd_batch_device_placed(G, method, order, B, syn, syn_flags, llr, llr_precision, status, base, readout,
+                                      osd0_out, osdw_out, corr_out, fail, stream, QD_OSD_ONCHIP);
+}
+
+int qd_osd_batch_device_placed(qd_graph* G, int32_t method, int32_t order, int64_t B, const uint8_t* syn,
+                               int32_t syn_flags, const void* llr, int32_t llr_precision, const uint8_t* status,
+                               const uint8_t* base, const uint8_t* readout, uint8_t* osd0_out, uint8_t* osdw_out,
+                               uint8_t* corr_out, uint8_t* fail, void* stream, int32_t placement) {
     return guarded([&] {
         check_graph(G);
         if (method < 0 || method > 2) throw Fail(-80, "osd method must be 0 (osd0), 1 (osd_e), 2 (osd_cs)");
         if (method == 1 && order > 20) throw Fail(-81, "osd_e order above 20 is not supported");
         if (method == 2 && order > 64) throw Fail(-82, "osd_cs order above 64 is not supported on the device");
         if (B < 0) throw Fail(-8, "negative batch");
+        check_osd_placement(placement);
         if (B == 0) return;
         if (!llr || (!syn && !syn_flags)) throw Fail(-83, "null OSD inputs");
         if (llr_precision != QD_F32 && llr_precision != QD_F64) throw Fail(-84, "invalid llr precision");
-        if (!osd_kernel_supports(G->dg)) throw Fail(-85, "graph too large for the device OSD (LDS image above 160 KiB)");
+        const bool onchip = placement != QD_OSD_HBM && osd_kernel_supports(G->dg);
+        OsdHbmLayout L;
+        if (!onchip) {
+            if (placement == QD_OSD_ONCHIP)
+                throw Fail(-85, "graph too large for the device OSD (LDS image above 160 KiB)");
+            if (!osd_hbm_choose(G->dg, &L))
+                throw Fail(-48, "graph too large for the HBM OSD kernel (its LDS part above 160 KiB, or k > 256)");
+        }
         if (fail && G->dg.k > 256) throw Fail(-86, "fused failure check after OSD supports <= 256 logicals");
-        if (B == 0) return;
+        if (G->host_only) throw Fail(-16, "host-only graph (qd_graph_create_host): no device to run OSD on");
         set_device(G);
         OsdArgs a{};
         a.B = B;
@@ -879,8 +966,54 @@ int qd_osd_batch_device(qd_graph* G, int32_t method, int32_t order, int64_t B, c
         a.osdw_out = osdw_out;
         a.corr_out = corr_out;
         a.fail = fail;
-        const int rc = launch_osd(G->dg, a, G->num_cus, (hipStream_t)stream);
+        int rc;
+        if (onchip) {
+            rc = launch_osd(G->dg, a, G->num_cus, (hipStream_t)stream);
+        } else {
+            const int64_t slots = osd_scratch_acquire(G, L, B, (hipStream_t)stream);
+            rc = launch_osd_hbm(G->dg, a, G->osd_ws, slots, (hipStream_t)stream);
+            osd_scratch_release(G, slots, (hipStream_t)stream);
+        }
         if (rc != 0) throw Fail(-104, std::string("osd launch failed: ") + hipGetErrorString((hipError_t)rc));
+    });
+}
+
+int qd_osd_kernel_info_placed(const qd_graph* G, int32_t placement, int64_t out[4]) {
+    int held = 0;
+    const int rc = guarded([&] {
+        if (out) out[0] = out[1] = out[2] = out[3] = 0;
+        check_osd_placement(placement);
+        if (!G) return;
+        OsdChoice c{0, 0, 0};
+        if (placement != QD_OSD_HBM && osd_choose(G->dg, &c)) {
+            if (out) out[0] = c.rs ? 0 : 1, out[1] = c.rs, out[2] = c.w, out[3] = c.lds;
+            held = 1;
+            return;
+        }
+        OsdHbmLayout L;
+        if (placement == QD_OSD_ONCHIP || !osd_hbm_choose(G->dg, &L)) return;
+        if (out) out[0] = 2, out[1] = 0, out[2] = L.W, out[3] = L.slot_bytes;
+        held = 1;
+    });
+    return rc != 0 ? rc : held;
+}
+
+int qd_osd_set_slots(qd_graph* G, int64_t slots) {
+    return guarded([&] {
+        check_graph(G);
+        if (slots < 0 || slots > (1ll << 20)) throw Fail(-47, "osd slots must be 0 (default) .. 2^20");
+        G->osd_slots_cfg = slots;
+    });
+}
+
+int qd_osd_hbm_info(const qd_graph* G, int64_t out[3]) {
+    return guarded([&] {
+        check_graph(G);
+        if (!out) throw Fail(-83, "null output");
+        OsdHbmLayout L;
+        out[0] = osd_hbm_choose(G->dg, &L) ? L.slot_bytes : 0;
+        out[1] = G->osd_slots_last;
+        out[2] = (int64_t)G->osd_ws_bytes;
     });
 }
 

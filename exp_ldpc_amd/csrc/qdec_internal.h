@@ -115,6 +115,26 @@ bool osd_choose(const DevGraph& g, OsdChoice* c);
 bool osd_kernel_supports(const DevGraph& g);
 int launch_osd(const DevGraph& g, const OsdArgs& a, int num_cus, hipStream_t stream);
 
+// osd_hbm_kernel (qdec_osd_hbm.hip): the same stage with the rows in a slot of
+// device memory.  Byte offsets of a slot (s_*: rows [m][W] u64, sort keys u64
+// and column indices u32 [ns], pos u32 [n], piv u32 [m], isp and out u8 [n];
+// every region 16-B aligned, the slot a multiple of 256 B) and of the
+// workgroup's LDS (l_*; the sort's chunk overlays the rest).
+struct OsdHbmLayout {
+    int64_t ns, W, RW;
+    int64_t s_rows, s_key, s_idx, s_pos, s_piv, s_isp, s_out, slot_bytes;
+    int64_t l_ctl, l_npv, l_x0, l_tcl, l_row, l_hit, l_skey, l_sidx, lds_bytes;
+    OsdHbmLayout() = default;
+    OsdHbmLayout(int64_t n, int64_t m);
+};
+// False: the kernel does not hold the graph (its LDS part above 160 KiB, or
+// k > 256).  No HIP call.
+bool osd_hbm_choose(const DevGraph& g, OsdHbmLayout* L);
+// `scratch` holds `slots` slots of L.slot_bytes; the grid is min(slots, B)
+int launch_osd_hbm(const DevGraph& g, const OsdArgs& a, void* scratch, int64_t slots, hipStream_t stream);
+// slots per CU of the HBM kernel by default (DESIGN §3.6c has the sweep)
+constexpr int kOsdHbmSlotsPerCu = 8;
+
 // ev[3] marks the end of a pre-pass inside the BP timing (the shot triage):
 // recorded with ev[0] and again after the pre-pass when one runs
 inline void record_ev(const DecodeArgs& a, int i, hipStream_t s) {

@@ -290,28 +290,47 @@ class Decoder:
     def osd_device_supported(self) -> bool:
         return bool(self._lib.qd_osd_device_supported(self._handle))
 
-    def osd_kernel_info(self):
+    def osd_kernel_info(self, rows: str = "onchip"):
         """(RS, W, dynamic LDS bytes) of the kernel osd_device launches for this
         graph (qd_osd_kernel_info; RS = 0: the workgroup kernel), or None when
-        no device kernel holds it.  No launch."""
-        return osd_kernel_info(self._handle)
+        no device kernel holds it.  With rows="hbm" / "auto" (see osd_device):
+        (kind, RS, W, bytes) of qd_osd_kernel_info_placed, kind 0 / 1 / 2 = the
+        register, workgroup or HBM kernel and bytes its dynamic LDS or, for the
+        HBM kernel, one slot.  No launch."""
+        return osd_kernel_info(self._handle, rows)
 
     def osd_device(self, B: int, *, llr, method: str = "osd_cs", order: int = 0, syn=None, syn_flags: int = 0,
                    status=None, base=None, readout=None, osd0=None, osdw=None, corr=None, fail=None,
-                   stream=None) -> None:
-        """Enqueue OSD (qd_osd_batch_device) for the shots whose `status` lacks
-        the BP-converged bit, on device buffers; `llr` is the BP soft output
-        (float32 or float64 tensor)."""
+                   stream=None, rows: str = "onchip") -> None:
+        """Enqueue OSD (qd_osd_batch_device_placed) for the shots whose `status`
+        lacks the BP-converged bit, on device buffers; `llr` is the BP soft
+        output (float32 or float64 tensor).  rows: where the kernel keeps the
+        augmented rows -- "onchip" (registers or LDS; QdecError -85 beyond 160
+        KiB), "hbm" (osd_hbm_kernel, a slot of device memory per workgroup) or
+        "auto" (on chip where a kernel holds the graph, else HBM).  The outputs
+        do not depend on it."""
         from .osd import OSD_METHODS
         if method not in OSD_METHODS:
             raise ValueError(f"unknown OSD method {method!r}")
         if stream is None:
             stream = _current_stream(self.device)
         prec = _abi.QD_F32 if str(getattr(llr, "dtype", "")).endswith("float32") else _abi.QD_F64
-        _abi.check(self._lib.qd_osd_batch_device(
+        _abi.check(self._lib.qd_osd_batch_device_placed(
             self._handle, OSD_METHODS[method], int(order), int(B), _abi.ptr(syn), int(syn_flags), _abi.ptr(llr), prec,
             _abi.ptr(status), _abi.ptr(base), _abi.ptr(readout), _abi.ptr(osd0), _abi.ptr(osdw), _abi.ptr(corr),
-            _abi.ptr(fail), C.c_void_p(stream)), "qd_osd_batch_device")
+            _abi.ptr(fail), C.c_void_p(stream), osd_rows_placement(rows)), "qd_osd_batch_device_placed")
+
+    def set_osd_slots(self, slots: int = 0) -> None:
+        """Slots (resident workgroups) of later rows="hbm" launches
+        (qd_osd_set_slots); 0 = the default.  Results do not depend on it."""
+        _abi.check(self._lib.qd_osd_set_slots(self._handle, int(slots)), "qd_osd_set_slots")
+
+    def osd_hbm_info(self) -> tuple[int, int, int]:
+        """(bytes per slot, slots of the last HBM launch, scratch bytes held);
+        qd_osd_hbm_info."""
+        out = np.zeros(3, np.int64)
+        _abi.check(self._lib.qd_osd_hbm_info(self._handle, _abi.ptr(out)), "qd_osd_hbm_info")
+        return int(out[0]), int(out[1]), int(out[2])
 
     def set_wave_occupancy(self, waves_per_cu: int = 0) -> None:
         """Waves per CU of the wave BP kernels (qd_graph_set_wave_occupancy):
@@ -418,9 +437,25 @@ class Decoder:
 QD_INPUT_PACKED = _abi.QD_INPUT_PACKED  # qd_syn_flags: bit-packed input rows
 
 
-def osd_kernel_info(handle):
+OSD_ROWS = {"onchip": _abi.QD_OSD_ONCHIP, "hbm": _abi.QD_OSD_HBM, "auto": _abi.QD_OSD_AUTO}
+
+
+def osd_rows_placement(rows) -> int:
+    """rows ("onchip" | "hbm" | "auto") -> QD_OSD_*."""
+    if rows not in OSD_ROWS:
+        raise ValueError(f"rows must be one of {sorted(OSD_ROWS)}, got {rows!r}")
+    return OSD_ROWS[rows]
+
+
+def osd_kernel_info(handle, rows: str = "onchip"):
     """Decoder.osd_kernel_info for a raw qd_graph handle (a host-only graph of
     qd_graph_create_host included)."""
+    if rows != "onchip":
+        out4 = np.zeros(4, np.int64)
+        rc = _abi.load().qd_osd_kernel_info_placed(handle, osd_rows_placement(rows), _abi.ptr(out4))
+        if rc < 0:
+            _abi.check(rc, "qd_osd_kernel_info_placed")
+        return tuple(int(v) for v in out4) if rc else None
     out = np.zeros(3, np.int32)
     if not _abi.load().qd_osd_kernel_info(handle, _abi.ptr(out)):
         return None

@@ -12,6 +12,9 @@ device.  Decoder modes (``--decoder_mode``):
   bpssf              BP + small-set-flip on H (R = 0); R >= 1 runs bpssf_hybrid
   bpssf_hybrid       BP on spacetime, fold, then BP+SSF on H     (build-defined)
   bp                 BP only on the spacetime matrix
+  bposd_detector     bpd_detector followed by OSD on the same graph for the shots BP
+                     leaves unconverged (under circuit noise nearly all of them);
+                     the OSD rows live in device memory (csrc/qdec_osd_hbm.hip)
   bpd_detector       BP on the fault check matrix of a detector error model
                      (_experiment.py:128-151).  Under depolarizing_noise the
                      storage experiment's Z-sector DEM is written by
@@ -24,11 +27,15 @@ device.  Decoder modes (``--decoder_mode``):
 
 A detector error model of the user's own (any noise model, Stim's DEM text) is
 sampled on the device from its fault probabilities and decoded in batches by
-``DemPipeline`` / ``run_dem_simulation`` (BP only, like ``BPDetectorCorrect``).
+``DemPipeline`` / ``run_dem_simulation`` (BP only by default, like
+``BPDetectorCorrect``; BP+OSD with ``osd=True``).
 
-OSD runs on the GPU for the shots BP did not converge on (Decoder.osd_device,
-csrc/qdec_osd.hip), fused with the fold and the failure check; graphs too large
-for that kernel use the host stage (osd.py).
+OSD runs on the GPU for the shots BP did not converge on (Decoder.osd_device),
+fused with the fold and the failure check: csrc/qdec_osd.hip with the rows on
+chip, csrc/qdec_osd_hbm.hip with the rows in device memory.  ``osd_rows`` says
+which: "onchip" (the existing modes' default: graphs past the 160 KiB LDS image
+use the host stage, osd.py), "auto" (on chip, else device memory;
+bposd_detector's default), "hbm", "host".
 Logical failure = any(Lz (readout + correction)) mod 2 as at _experiment.py:209
 (computed in-kernel for device stages).
 """
@@ -58,7 +65,39 @@ __all__ = ["DECODER_MODES", "BatchPipeline", "DemPipeline", "run_dem_simulation"
            "BPSSFCorrect", "BPDetectorCorrect", "run_simulation", "add_bposd_args", "unpack_bposd_args", "load_code", "p_sweep",
            "p_sweep_main", "parse_sweep_spec"]
 
-DECODER_MODES = ["bposd", "bposd_single_shot", "bposd_hybrid", "bpd_detector", "bpssf", "bpssf_hybrid", "bp"]
+DECODER_MODES = ["bposd", "bposd_single_shot", "bposd_hybrid", "bpd_detector", "bposd_detector", "bpssf",
+                 "bpssf_hybrid", "bp"]
+# where the OSD stage of a pipeline runs: a device kernel with its rows on chip
+# (the host stage beyond 160 KiB), on chip or else in HBM, always in HBM, or the host stage
+OSD_ROWS = ("onchip", "auto", "hbm", "host")
+DEFAULT_LLR_BUDGET = 4 << 30  # bytes of BP soft output a DEM decode with OSD holds at a time
+
+
+def _check_osd_rows(osd_rows, default):
+    if osd_rows is None:
+        return default
+    if osd_rows not in OSD_ROWS:
+        raise ValueError(f"osd_rows must be one of {OSD_ROWS} or None, got {osd_rows!r}")
+    return osd_rows
+
+
+def _osd_rows_for(dec, osd_rows):
+    """The rows= argument of dec.osd_device under a pipeline's osd_rows, or None
+    for the host stage."""
+    if osd_rows == "host":
+        return None
+    if osd_rows == "hbm":
+        return "hbm"
+    if dec.osd_device_supported:
+        return "onchip"
+    if osd_rows == "auto" and dec.osd_kernel_info("auto") is not None:
+        return "auto"
+    return None
+
+
+def _llr_chunk(B, n, itemsize, budget):
+    """Shots per sub-batch so that an [shots][n] llr buffer stays within `budget` bytes."""
+    return max(1, min(int(B), int(budget) // max(1, int(n) * int(itemsize))))
 DEFAULT_SEED = 20250221
 
 
@@ -85,13 +124,31 @@ class DemPipeline:
     with the fault priors and the fault map F as logicals.  The sampler writes the
     fault vector e and H e; the decode takes e as its ``readout``, so its fused
     check any(F (e ^ x)) = any(F e ^ F x) = any(obs ^ F x) is the reference's
-    failure flag (:143-151, :204).  BP only, like the reference's class."""
+    failure flag (:143-151, :204).  BP only by default, like the reference's class
+    (bp_osd_options may carry osd_method and never switch OSD on by themselves).
 
-    def __init__(self, detector_error_model, bp_osd_options: Dict, *, device: int = 0, precision: str = "f64"):
+    osd=True: the shots BP leaves unconverged go through OSD (osd_method and
+    osd_order of bp_osd_options) on the same graph, and their flag is any(obs ^
+    F x) of the OSD solution.  osd_rows: "auto" (a device kernel, its rows on
+    chip or in HBM), "onchip" (the host stage beyond 160 KiB), "hbm", "host".
+    The [shots][faults] llr buffer is kept within llr_budget_bytes by decoding
+    in sub-batches; the flags do not depend on the split."""
+
+    def __init__(self, detector_error_model, bp_osd_options: Dict, *, device: int = 0, precision: str = "f64",
+                 osd: bool = False, osd_rows: str = "auto", osd_threads: int = 0,
+                 llr_budget_bytes: int = DEFAULT_LLR_BUDGET):
         from .dem import DetectorSpacetimeCode
         self.dem = DetectorSpacetimeCode(detector_error_model)
         self.device = int(device)
         o = bp_osd_options
+        self.osd = bool(osd)
+        self.osd_rows = _check_osd_rows(osd_rows, "auto")
+        self.llr_budget_bytes = int(llr_budget_bytes)
+        if self.llr_budget_bytes <= 0:
+            raise ValueError("llr_budget_bytes must be positive")
+        self.osd_method, self.osd_order = o.get("osd_method", "osd_cs"), int(o.get("osd_order", 0))
+        self.osd_solver = (OsdSolver(self.dem.fault_check_matrix, self.osd_method, self.osd_order, osd_threads)
+                           if self.osd else None)
         fmap = self.dem.fault_map
         self.k = fmap.shape[0]
         # the fault map stays sparse: Decoder.set_logicals hands over CSR supports,
@@ -115,6 +172,8 @@ class DemPipeline:
         torch = _torch()
         B = int(B)
         dev = torch.device("cuda", self.device)
+        if self.osd:
+            return self._run_osd(B, seed, stream_id, shot0, want_detail)
         with torch.cuda.device(dev):
             det, faults, obs = sample_dem_device(self.dec, B, seed, stream_id, shot0, packed=packed,
                                                  want_obs=want_detail)
@@ -136,15 +195,66 @@ class DemPipeline:
                                iters_sum=int(iters.to(torch.int64).sum().item()), ssf_steps_sum=0, detail=detail)
 
 
+    def _run_osd(self, B, seed, stream_id, shot0, want_detail):
+        """run() with the OSD stage: byte rows (the OSD kernels read them), in
+        sub-batches under the llr budget; the sampler is counter-based, so the
+        shots do not depend on the split."""
+        from .dem import sample_dem_device
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        dec = self.dec
+        f64 = dec.precision != _abi.QD_F32
+        step = _llr_chunk(B, dec.n, 8 if f64 else 4, self.llr_budget_bytes)
+        rows = _osd_rows_for(dec, self.osd_rows)
+        F = sp.csr_matrix(self.dem.fault_map).astype(np.int64) if self.k else None
+        fail_h = np.zeros(B, bool)
+        parts = {"det": [], "obs": [], "iters": [], "status": []}
+        conv = iters_sum = 0
+        with torch.cuda.device(dev):
+            for lo in range(0, B, step):
+                b = min(B, lo + step) - lo
+                det, faults, obs = sample_dem_device(dec, b, seed, stream_id, shot0 + lo, packed=False,
+                                                     want_obs=want_detail)
+                iters = torch.zeros(b, dtype=torch.int32, device=dev)
+                status = torch.zeros(b, dtype=torch.uint8, device=dev)
+                fail = torch.zeros(b, dtype=torch.uint8, device=dev)
+                llr = torch.empty((b, dec.n), dtype=torch.float64 if f64 else torch.float32, device=dev)
+                rd, fl = (faults, fail) if self.k else (None, None)
+                dec.decode_device(b, syn=det, readout=rd, llr=llr, iters=iters, status=status, fail=fl)
+                if rows:
+                    dec.osd_device(b, llr=llr, method=self.osd_method, order=self.osd_order, syn=det, status=status,
+                                   readout=rd, fail=fl, rows=rows)
+                f_h = fail.cpu().numpy().astype(bool)
+                bad = torch.nonzero((status & 1) == 0).flatten()
+                if not rows and self.k and bad.numel():
+                    _, ow = self.osd_solver.solve(det.index_select(0, bad).cpu().numpy(),
+                                                  llr.index_select(0, bad).double().cpu().numpy())
+                    diff = sp.csr_matrix((faults.index_select(0, bad).cpu().numpy() ^ ow).astype(np.int64))
+                    f_h[bad.cpu().numpy()] = np.asarray((diff @ F.T).toarray() % 2).any(axis=1)
+                fail_h[lo:lo + b] = f_h
+                conv += int((status & 1).sum().item())
+                iters_sum += int(iters.to(torch.int64).sum().item())
+                if want_detail:
+                    parts["det"].append(det.cpu().numpy())
+                    parts["obs"].append(obs.cpu().numpy() if obs is not None else np.zeros((b, 0), np.uint8))
+                    parts["iters"].append(iters.cpu().numpy())
+                    parts["status"].append(status.cpu().numpy())
+        detail = {k: np.concatenate(v) for k, v in parts.items()} if want_detail else None
+        return BatchResult(fail=fail_h, bp_converged=conv, iters_sum=iters_sum, ssf_steps_sum=0, detail=detail)
+
+
 def run_dem_simulation(samples, detector_error_model, bp_osd_options, *, seed: int, stream_id: int = 0,
                        shot0: int = 0, device: int = 0, batch: int = 1 << 18, precision: str = "f64",
-                       stats: dict | None = None):
+                       stats: dict | None = None, osd: bool = False, osd_rows: str = "auto",
+                       llr_budget_bytes: int = DEFAULT_LLR_BUDGET):
     """Sample and decode `samples` shots of a detector error model (DEM text or a
     parsed model) on one GPU; returns a bool ndarray of logical-failure flags,
     shaped like run_simulation's.  Replaces the reference's per-shot loop over
     Stim's detector samples and BPDetectorCorrect (_experiment.py:186-209) for a
-    user-supplied DEM; the flags do not depend on `batch`."""
-    pipe = DemPipeline(detector_error_model, bp_osd_options, device=device, precision=precision)
+    user-supplied DEM; the flags do not depend on `batch`.  osd=True: BP+OSD
+    (DemPipeline's osd, osd_rows, llr_budget_bytes)."""
+    pipe = DemPipeline(detector_error_model, bp_osd_options, device=device, precision=precision, osd=osd,
+                       osd_rows=osd_rows, llr_budget_bytes=llr_budget_bytes)
     out = np.zeros(samples, dtype=bool)
     agg = {"bp_converged": 0, "iters_sum": 0, "ssf_steps_sum": 0}
     for start in range(0, samples, batch):
@@ -165,13 +275,20 @@ class BatchPipeline:
 
     def __init__(self, code, rounds: int, mode: str, bp_osd_options: Dict, priors: Tuple[float, float], *,
                  device: int = 0, precision: str = "f64", use_x_logicals: bool = False, osd_threads: int = 0,
-                 noise=None, dem_source: str | None = None, sim=None):
+                 noise=None, dem_source: str | None = None, sim=None, osd_rows: str | None = None,
+                 llr_budget_bytes: int = DEFAULT_LLR_BUDGET):
         if mode not in DECODER_MODES:
             raise RuntimeError("Unknown decoder operation mode")
         if dem_source not in (None, "circuit"):
             raise ValueError('dem_source is None (by noise model) or "circuit"')
-        if dem_source is not None and mode != "bpd_detector":
-            raise ValueError("dem_source applies to bpd_detector only")
+        if dem_source is not None and mode not in ("bpd_detector", "bposd_detector"):
+            raise ValueError("dem_source applies to bpd_detector and bposd_detector only")
+        # None: the existing modes keep their selection (on chip, else the host
+        # stage); the DEM mode's graphs are past the LDS limit, so it takes HBM
+        self.osd_rows = _check_osd_rows(osd_rows, "auto" if mode == "bposd_detector" else "onchip")
+        self.llr_budget_bytes = int(llr_budget_bytes)
+        if self.llr_budget_bytes <= 0:
+            raise ValueError("llr_budget_bytes must be positive")
         self.dem_source = None
         if mode == "bpssf" and rounds > 0:
             mode = "bpssf_hybrid"
@@ -217,7 +334,7 @@ class BatchPipeline:
             prior[n:] = meas_prior
             self.ss = Decoder(Hss, prior, n_data=n, fold_blocks=1, **common)
             self.ss_osd = OsdSolver(Hss, osd_method, osd_order, osd_threads)
-        if mode == "bpd_detector":
+        if mode in ("bpd_detector", "bposd_detector"):
             # reference BPDetectorCorrect (_experiment.py:128-151): BP (no OSD) on the
             # DEM's fault check matrix with its fault priors.  The sampler's
             # spacetime syndrome is the DEM's detector vector; the readout-flip
@@ -226,11 +343,15 @@ class BatchPipeline:
             # check any(F (v ^ x)) = any(obs ^ F x) is the reference's failure flag.
             kind = getattr(noise, "kind", "")
             if noise is None or (dem_source is None and kind == "trivial"):
-                raise NotImplementedError("bpd_detector needs a noise model with errors to build its DEM from")
+                raise NotImplementedError(f"{mode} needs a noise model with errors to build its DEM from")
             if dem_source == "circuit" or kind != "depolarizing":
                 self._init_circuit_dem(code, noise, use_x_logicals, common, sim)
             else:
                 self._init_storage_dem(noise, common)
+            # bposd_detector: OSD on the same graph for the shots BP leaves
+            # unconverged (under circuit noise nearly all of them)
+            self.det_osd = (OsdSolver(self.dem.fault_check_matrix, osd_method, osd_order, osd_threads)
+                            if mode == "bposd_detector" else None)
         # a plain-H decoder for the sampler
         self.sampler_graph = Decoder(self.H, 0.01, device=self.device)
 
@@ -327,6 +448,61 @@ class BatchPipeline:
         _, ow = osd.solve(s, llr)
         return idx, ow
 
+    def _circuit_readout_faults(self, readout, lo, hi):
+        """Circuit-DEM path: the fault-length `readout` r = T obs of shots lo .. hi
+        (obs = L readout on the pivot columns of F, zero elsewhere), so F r = obs."""
+        torch = _torch()
+        dev = readout.device
+        L = torch.from_numpy(np.asarray(sp.csr_matrix(self.L).toarray() % 2, dtype=np.float32)).to(dev)
+        obs = torch.remainder(readout[lo:hi].to(torch.float32) @ L.T, 2)               # exact: sums <= n < 2^24
+        T = torch.from_numpy(self._obs_solve).to(dev)
+        v = torch.zeros((hi - lo, self.n_faults), dtype=torch.uint8, device=dev)
+        v[:, torch.from_numpy(self._obs_pivots).to(dev)] = torch.remainder(obs @ T.T, 2).to(torch.uint8)
+        return v
+
+    def _run_bposd_detector(self, syn, readout, iters, status, fail):
+        """BP on the DEM graph, then OSD for the shots it leaves unconverged; the
+        flag is any(obs ^ F x) with x the OSD solution there (fused in the OSD
+        kernel's failure check, as in the BP kernel's).  The llr buffer is
+        [shots][n_faults], so the batch is decoded in sub-batches that keep it
+        within llr_budget_bytes; the flags do not depend on the split.  Returns
+        [(idx, flags)] of the shots whose OSD ran on the host."""
+        torch = _torch()
+        B, dev, nf, n = syn.shape[0], syn.device, self.n_faults, self.n
+        dec = self.det
+        has_obs = self.L.shape[0] > 0
+        f64 = dec.precision != _abi.QD_F32
+        step = _llr_chunk(B, nf, 8 if f64 else 4, self.llr_budget_bytes)
+        rows = _osd_rows_for(dec, self.osd_rows)
+        F = sp.csr_matrix(self.dem.fault_map).astype(np.int64) if has_obs else None
+        fixes = []
+        for lo in range(0, B, step):
+            hi = min(B, lo + step)
+            b = hi - lo
+            v = None
+            if has_obs and self.dem_source == "circuit":
+                v = self._circuit_readout_faults(readout, lo, hi)
+            elif has_obs:
+                v = torch.zeros((b, nf), dtype=torch.uint8, device=dev)
+                v[:, nf - n:] = readout[lo:hi]
+            llr = torch.empty((b, nf), dtype=torch.float64 if f64 else torch.float32, device=dev)
+            s, st = syn[lo:hi], status[lo:hi]
+            fl = fail[lo:hi] if has_obs else None
+            dec.decode_device(b, syn=s, readout=v, llr=llr, iters=iters[lo:hi], status=st, fail=fl)
+            if rows:
+                dec.osd_device(b, llr=llr, method=self.osd_method, order=self.osd_order, syn=s, status=st, readout=v,
+                               fail=fl, rows=rows)
+                continue
+            bad = torch.nonzero((st & 1) == 0).flatten()
+            if bad.numel() == 0 or not has_obs:
+                continue
+            _, ow = self.det_osd.solve(s.index_select(0, bad).cpu().numpy(),
+                                       llr.index_select(0, bad).double().cpu().numpy())
+            diff = sp.csr_matrix((v.index_select(0, bad).cpu().numpy() ^ ow).astype(np.int64))
+            flags = np.asarray((diff @ F.T).toarray() % 2).any(axis=1)
+            fixes.append((lo + bad.cpu().numpy(), flags))
+        return fixes
+
     def run(self, syn, readout, want_corrections: bool = False) -> BatchResult:
         torch = _torch()
         B = syn.shape[0]
@@ -340,6 +516,7 @@ class BatchPipeline:
         steps = torch.zeros(B, **i32)
         corr = torch.zeros((B, n), **u8)
         host_fix = None  # (idx, corrections) applied on host
+        fail_fix = []    # (idx, flags) of shots whose OSD ran on the host without a correction to fold
         mode = self.mode
         if mode in ("bp", "bposd"):
             need_llr = mode == "bposd"
@@ -347,9 +524,10 @@ class BatchPipeline:
                               else torch.float64, device=dev) if need_llr else None
             self.st.decode_device(B, syn=syn, readout=readout, corr=corr, llr=llr, iters=iters, status=status,
                                   fail=fail)
-            if need_llr and self.st.osd_device_supported:
+            rows = _osd_rows_for(self.st, self.osd_rows) if need_llr else None
+            if rows:
                 self.st.osd_device(B, llr=llr, method=self.osd_method, order=self.osd_order, syn=syn, status=status,
-                                   readout=readout, corr=corr, fail=fail)
+                                   readout=readout, corr=corr, fail=fail, rows=rows)
             elif need_llr:
                 idx, ow = self._osd_fix(self.st, self.st_osd, syn, status, llr, B)
                 if idx is not None:
@@ -368,10 +546,11 @@ class BatchPipeline:
                                   else torch.float64, device=dev)
                 self.fin.decode_device(B, base=c1, readout=readout, corr=corr, llr=llr, status=status, fail=fail,
                                        syn_flags=3)
-                bad = torch.nonzero((status & 1) == 0).flatten() if not self.fin.osd_device_supported else None
+                rows = _osd_rows_for(self.fin, self.osd_rows)
+                bad = torch.nonzero((status & 1) == 0).flatten() if not rows else None
                 if bad is None:
                     self.fin.osd_device(B, llr=llr, method=self.osd_method, order=self.osd_order, syn_flags=3,
-                                        status=status, base=c1, readout=readout, corr=corr, fail=fail)
+                                        status=status, base=c1, readout=readout, corr=corr, fail=fail, rows=rows)
                 elif bad.numel():
                     idx = bad.cpu().numpy()
                     v = (readout.index_select(0, bad) ^ c1.index_select(0, bad)).cpu().numpy()
@@ -381,14 +560,12 @@ class BatchPipeline:
         elif mode == "bpssf":
             self.fin.decode_device(B, syn=syn, readout=readout, corr=corr, iters=iters, status=status,
                                    ssf_steps=steps, fail=fail)
+        elif mode == "bposd_detector":
+            fail_fix = self._run_bposd_detector(syn, readout, iters, status, fail)
         elif mode == "bpd_detector" and self.dem_source == "circuit":
             # syn: the circuit's detectors (StorageSim.sample_detectors_device)
             if self.L.shape[0]:
-                L = torch.from_numpy(np.asarray(sp.csr_matrix(self.L).toarray() % 2, dtype=np.float32)).to(dev)
-                obs = torch.remainder(readout.to(torch.float32) @ L.T, 2)               # exact: sums <= n < 2^24
-                T = torch.from_numpy(self._obs_solve).to(dev)
-                v = torch.zeros((B, self.n_faults), **u8)
-                v[:, torch.from_numpy(self._obs_pivots).to(dev)] = torch.remainder(obs @ T.T, 2).to(torch.uint8)
+                v = self._circuit_readout_faults(readout, 0, B)
                 self.det.decode_device(B, syn=syn, readout=v, iters=iters, status=status, fail=fail)
             else:  # no observable: nothing can fail
                 self.det.decode_device(B, syn=syn, iters=iters, status=status)
@@ -409,10 +586,11 @@ class BatchPipeline:
                 new_acc = torch.empty((B, n), **u8)
                 s_in = raw.contiguous()
                 self.ss.decode_device(B, syn=s_in, base=acc, corr=new_acc, llr=llr, status=st_t, syn_flags=1)
-                bad = torch.nonzero((st_t & 1) == 0).flatten() if not self.ss.osd_device_supported else None
+                rows = _osd_rows_for(self.ss, self.osd_rows)
+                bad = torch.nonzero((st_t & 1) == 0).flatten() if not rows else None
                 if bad is None:
                     self.ss.osd_device(B, llr=llr, method=self.osd_method, order=self.osd_order, syn=s_in,
-                                       syn_flags=1, status=st_t, base=acc, corr=new_acc)
+                                       syn_flags=1, status=st_t, base=acc, corr=new_acc, rows=rows)
                 elif bad.numel():
                     a_h = acc.index_select(0, bad).cpu().numpy()
                     s_h = s_in.index_select(0, bad).cpu().numpy() ^ ((self.H @ a_h.T).T % 2).astype(np.uint8)
@@ -423,10 +601,11 @@ class BatchPipeline:
                               device=dev)
             self.fin.decode_device(B, base=acc, readout=readout, corr=corr, llr=llr, iters=iters, status=status,
                                    fail=fail, syn_flags=3)
-            bad = torch.nonzero((status & 1) == 0).flatten() if not self.fin.osd_device_supported else None
+            rows = _osd_rows_for(self.fin, self.osd_rows)
+            bad = torch.nonzero((status & 1) == 0).flatten() if not rows else None
             if bad is None:
                 self.fin.osd_device(B, llr=llr, method=self.osd_method, order=self.osd_order, syn_flags=3,
-                                    status=status, base=acc, readout=readout, corr=corr, fail=fail)
+                                    status=status, base=acc, readout=readout, corr=corr, fail=fail, rows=rows)
             elif bad.numel():
                 idx = bad.cpu().numpy()
                 a_h = acc.index_select(0, bad).cpu().numpy()
@@ -440,6 +619,8 @@ class BatchPipeline:
             idx, c = host_fix
             corr_h[idx] = c
             fail_h[idx] = self._fail_host(readout.index_select(0, torch.from_numpy(idx).to(dev)).cpu().numpy(), c)
+        for idx, flags in fail_fix:
+            fail_h[idx] = flags
         return BatchResult(fail=fail_h, bp_converged=int((status & 1).sum().item()),
                            iters_sum=int(iters.to(torch.int64).sum().item()),
                            ssf_steps_sum=int(steps.to(torch.int64).sum().item()),
@@ -526,7 +707,8 @@ def _steps(checks):
 def run_simulation(samples, code, meas_prior, data_prior, noise_model, noise_model_args, bp_osd_options, rounds,
                    decoder_mode, *, seed: int = DEFAULT_SEED, stream_id: int = 0, shot0: int = 0, device: int = 0,
                    batch: int = 1 << 18, precision: str = "f64", stats: dict | None = None,
-                   dem_source: str | None = None):
+                   dem_source: str | None = None, osd_rows: str | None = None,
+                   llr_budget_bytes: int = DEFAULT_LLR_BUDGET):
     """Sample and decode `samples` shots on one GPU; returns a bool ndarray of
     logical-failure flags (reference run_simulation, _experiment.py:154-210,
     which returns a list of the same flags).  dem_source="circuit": bpd_detector
@@ -538,7 +720,8 @@ def run_simulation(samples, code, meas_prior, data_prior, noise_model, noise_mod
     mp = meas_prior(x_steps, z_steps)
     dp = data_prior(x_steps, z_steps)
     pipe = BatchPipeline(code, rounds, decoder_mode, bp_osd_options, (dp, mp), device=device, precision=precision,
-                         noise=noise_model(**noise_model_args), dem_source=dem_source, sim=sim)
+                         noise=noise_model(**noise_model_args), dem_source=dem_source, sim=sim, osd_rows=osd_rows,
+                         llr_budget_bytes=llr_budget_bytes)
     out = np.zeros(samples, dtype=bool)
     agg = {"bp_converged": 0, "iters_sum": 0, "ssf_steps_sum": 0}
     with torch.cuda.device(device):
@@ -734,7 +917,7 @@ HBM_PEAK_BYTES_S = 8.0e12  # MI355X HBM3E peak (MI355X_MICROARCH.md)
 
 def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_prior, *, gpus: int | None = None,
             devices=None, seed: int = DEFAULT_SEED, batch: int = 1 << 18, precision: str = "f64",
-            checkpoint: str | None = None, dem_source: str | None = None, **kwargs):
+            checkpoint: str | None = None, dem_source: str | None = None, osd_rows: str | None = None, **kwargs):
     """Sweep the physical error rate (reference p_sweep, misc/p_sweep.py:17-40).
     Shots are sharded over `gpus` devices by index (shard d decodes a
     contiguous shot range); exactly `samples` shots per point.  `devices`
@@ -758,7 +941,8 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
     writes its CSV only at the end (misc/p_sweep.py:78).
 
     dem_source: BatchPipeline's; points decoded on the circuit's own DEM carry
-    dem_sector = "circuit"."""
+    dem_sector = "circuit".  osd_rows: BatchPipeline's (where the OSD stage runs;
+    the failure counts do not depend on it)."""
     import pandas as pd
     torch = _torch()
     done = _load_checkpoint(checkpoint)
@@ -786,7 +970,7 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
 
         def pipeline(d):
             return BatchPipeline(code, rounds, mode, bp_osd_options, (dp, mp), device=d, precision=precision,
-                                 noise=nm, dem_source=dem_source, sim=sim)
+                                 noise=nm, dem_source=dem_source, sim=sim, osd_rows=osd_rows)
         pipes = [pipeline(d) for d in devs]
         per = math.ceil(samples / ndev)
         shards = [(i, i * per, min(samples, (i + 1) * per)) for i in range(ndev)]
@@ -838,7 +1022,7 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
         point["config_fp"] = fp
         if pipes[0].dem_source == "circuit":
             point["dem_sector"] = "circuit"          # dem.detector_error_model of the sampled circuit
-        elif mode == "bpd_detector" and rounds >= 2:
+        elif mode in ("bpd_detector", "bposd_detector") and rounds >= 2:
             point["dem_sector"] = "z_only_unpinned"  # see BatchPipeline's warning / dem.storage_experiment_dem
         data.append(point)
         if checkpoint:
@@ -886,6 +1070,10 @@ def p_sweep_main(noise_model_args, noise_model, meas_prior, data_prior):
     parser.add_argument("--batch", type=int, default=1 << 18, help="shots per device launch")
     parser.add_argument("--precision", choices=["f32", "f64"], default="f64",
                         help="BP message precision (default f64, as ldpc v1; f32 is the faster stated-tolerance variant)")
+    parser.add_argument("--osd_rows", choices=list(OSD_ROWS), default=None,
+                        help="where the OSD stage runs: device kernel with rows on chip (host stage beyond 160 KiB), "
+                             "on chip or else in HBM, always in HBM, or the host stage (default: onchip; auto for "
+                             "bposd_detector)")
     parser.add_argument("--checkpoint", type=str, default=None,
                         help="CSV that each finished point is appended to; finished points are skipped on restart")
     args = parser.parse_args(sys.argv[1:])
@@ -896,6 +1084,6 @@ def p_sweep_main(noise_model_args, noise_model, meas_prior, data_prior):
                      noise_model_args=noise_model_args, meas_prior=meas_prior, data_prior=data_prior,
                      p_values=sweep, decoder_mode=args.decoder_mode, bp_osd_options=bp_osd_options,
                      gpus=args.gpus, devices=args.devices, seed=args.seed, batch=args.batch, precision=args.precision,
-                     checkpoint=args.checkpoint)
+                     checkpoint=args.checkpoint, osd_rows=args.osd_rows)
     result.to_csv(sys.stdout)
     return result

@@ -1,9 +1,13 @@
 """Ordered-statistics decoding stage, host side (C++ in libqdec_hip.so,
 qd_osd_batch).  The batched pipelines use the GPU version
-(Decoder.osd_device -> qd_osd_batch_device, csrc/qdec_osd.hip, bit-identical)
-whenever a device kernel holds the graph (Decoder.osd_device_supported: rows in
-registers for m <= 384 and n < 1024, rows in LDS up to a 160 KiB image); this
-host stage serves the single-shot ldpc-compatible API and larger graphs.
+(Decoder.osd_device -> qd_osd_batch_device_placed, bit-identical) whenever a
+device kernel holds the graph: csrc/qdec_osd.hip with the rows on chip
+(Decoder.osd_device_supported: registers for m <= 384 and n < 1024, LDS up to a
+160 KiB image), csrc/qdec_osd_hbm.hip with the rows in device memory beyond that
+(rows="hbm" / "auto": circuit detector error models, deep spacetime graphs).
+This host stage serves the single-shot ldpc-compatible API, the pipelines'
+osd_rows="host", the existing modes' default beyond 160 KiB (osd_rows="onchip"),
+and it is the yardstick of tools/bench_osd_hbm.py.
 
 Post-processes the BP soft output of shots BP did not converge on, as ldpc v1's
 ``bposd_decoder`` does (reference call sites python/qldpc/misc/_experiment.py:23,

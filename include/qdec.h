@@ -365,6 +365,44 @@ int qd_osd_batch_device(qd_graph* g, int32_t method, int32_t order, int64_t B, c
                         const uint8_t* readout, uint8_t* osd0_out, uint8_t* osdw_out, uint8_t* corr_out, uint8_t* fail,
                         void* stream);
 
+/* Where the OSD stage keeps the augmented rows [H_sorted | s].  On chip
+ * (registers or LDS) is the selection above.  In HBM, osd_hbm_kernel gives every
+ * workgroup a slot of a scratch the graph handle owns: the rows (m x ceil((n +
+ * 1) / 64) words), the sort keys and indices, and the solution; indices are
+ * 32-bit, so circuit detector error models (648 x 25,684: 2 MiB of rows) and
+ * deep spacetime graphs are decoded on the device.  Same spec and outputs,
+ * bit-identical to qd_osd_batch.  The HBM kernel holds a graph while its LDS
+ * part (m hit flags, four row buffers, 64 transformed columns) fits 160 KiB and
+ * k <= 256 (-48 otherwise).
+ *
+ * The scratch is allocated at the first HBM launch and grown on demand: num_cus
+ * x 8 slots by default (qd_osd_set_slots: any count; -47 for slots < 0 or >
+ * 2^20), at most B, at most a quarter of the free device memory (-45 when that
+ * does not hold one slot).  On an allocation failure the slot count is halved
+ * down to one; only then the launch fails with -46.  Launches on one handle from
+ * different streams are chained through an event of the handle; a regrow and
+ * qd_graph_destroy wait for it.  Results never depend on the slot count. */
+#define QD_OSD_ONCHIP 0 /* qd_osd_batch_device's selection, -85 beyond it */
+#define QD_OSD_HBM 1    /* always the HBM kernel */
+#define QD_OSD_AUTO 2   /* on chip where a kernel holds the graph, else HBM */
+/* qd_osd_batch_device with a placement (-44 for any other value; -16 on a
+ * host-only graph); qd_osd_batch_device is this call with QD_OSD_ONCHIP. */
+int qd_osd_batch_device_placed(qd_graph* g, int32_t method, int32_t order, int64_t B, const uint8_t* syn,
+                               int32_t syn_flags, const void* llr, int32_t llr_precision, const uint8_t* status,
+                               const uint8_t* base, const uint8_t* readout, uint8_t* osd0_out, uint8_t* osdw_out,
+                               uint8_t* corr_out, uint8_t* fail, void* stream, int32_t placement);
+/* The kernel a placement launches; no HIP call, host-only graphs answer.  out[0] =
+ * kind (0 register kernel, 1 workgroup kernel, 2 HBM kernel), out[1] = RS (0 unless
+ * kind 0), out[2] = W, out[3] = dynamic LDS bytes (kinds 0, 1) or bytes per slot
+ * (kind 2).  Returns 1, 0 (out all zero) when the placement has no kernel for the
+ * graph, -44 for an unknown placement. */
+int qd_osd_kernel_info_placed(const qd_graph* g, int32_t placement, int64_t out[4]);
+/* Slots of the next HBM launches (0 = the default). */
+int qd_osd_set_slots(qd_graph* g, int64_t slots);
+/* out[0] = bytes per slot (0: the HBM kernel does not hold the graph), out[1] =
+ * slots of the last HBM launch, out[2] = scratch bytes held. */
+int qd_osd_hbm_info(const qd_graph* g, int64_t out[3]);
+
 /* Kernel timing for measurement: with capacity > 0, the next `capacity` decode
  * calls record HIP events on their launch stream immediately before the BP kernel,
  * after it and after the SSF kernel.  qd_graph_read_timing returns the per-call
