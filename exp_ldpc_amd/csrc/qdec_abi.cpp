@@ -1241,6 +1241,22 @@ int qd_graph_plan_names(const qd_graph* G, const qd_params* p, int64_t B, uint32
     });
 }
 
+int64_t qd_kernel_table_names(char* buf, int64_t cap) {
+    int64_t len = 0;
+    const int e = guarded([&] {
+        std::string s;
+        append_wave_kernel_names(s);
+        append_block_kernel_names(s);
+        len = (int64_t)s.size();
+        if (buf && cap > 0) {
+            const size_t k = std::min<size_t>(s.size(), (size_t)cap - 1);
+            std::memcpy(buf, s.data(), k);
+            buf[k] = 0;
+        }
+    });
+    return e ? e : len;
+}
+
 int qd_graph_it1_tables_copy(const qd_graph* G, int32_t precision, uint16_t* lut, uint64_t* vchk, int32_t* n_pad) {
     return guarded([&] {
         check_graph(G);

@@ -177,6 +177,11 @@ struct LaunchNames {
 };
 LaunchNames& last_launch_names();
 inline const char* noted_name(const KernelEntry* e) { return e && e->noted ? e->name.c_str() : ""; }
+// The name of every entry of the families' tables, one per line, in table order
+// (wave_tables, qdec_launch_wave.hip; block_tables, qdec_launch_block.hip).  No
+// HIP call.  Read by qd_kernel_table_names.
+void append_wave_kernel_names(std::string& out);
+void append_block_kernel_names(std::string& out);
 
 // ---------------------------------------------------------------- launch plan
 // Everything a decode decides before its first launch, decided once

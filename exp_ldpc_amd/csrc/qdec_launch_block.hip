@@ -49,6 +49,12 @@ static const BlockTables& block_tables() {
     return tables;
 }
 
+void append_block_kernel_names(std::string& out) {
+    const BlockTables& t = block_tables();
+    for (const KernelTable* tab : {&t.block, &t.group, &t.lds, &t.lds64, &t.ssf})
+        for (const KernelEntry& e : *tab) out += e.name + "\n";
+}
+
 const KernelEntry* ssf_block_entry(int path) {
     const BlockTables& t = block_tables();
     if (path == kFinIncBlock) return &t.ssf[0];

@@ -45,6 +45,12 @@ static const WaveTables& wave_tables() {
     return tables;
 }
 
+void append_wave_kernel_names(std::string& out) {
+    const WaveTables& t = wave_tables();
+    for (const KernelTable* tab : {&t.bp_wave, &t.ms_wave, &t.ms_cmp, &t.triage, &t.ssf_wave, &t.ssf_lut})
+        for (const KernelEntry& e : *tab) out += e.name + "\n";
+}
+
 // ---------------------------------------------------------------- launch plan
 // Wave graphs.  Lean launches: no x / corr / llr outputs, no base, no syndrome
 // flags, no fold (and, with SSF, the packed queue).  The two-pass path

@@ -565,6 +565,15 @@ int qd_graph_plan(const qd_graph* g, const qd_params* p, int64_t B, uint32_t pre
  * counterpart. */
 int qd_graph_plan_names(const qd_graph* g, const qd_params* p, int64_t B, uint32_t present, char* bp,
                         int32_t bp_len, char* ssf, int32_t ssf_len, char* pre, int32_t pre_len);
+/* Every instantiation the library builds for the decode kernel families: the
+ * names of all entries of the kernel tables the plan picks from (wave graphs
+ * first, then workgroup graphs; table order), each followed by '\n', spelled as
+ * qd_graph_plan_names spells them; the workgroup SSF kernels, which the plan
+ * reports as "", are listed under their own names.  Returns the length of the
+ * list; copies it into buf (NUL-terminated, cut to cap) when buf is given.  No
+ * HIP call.  For tests that keep a ledger of which instantiations they launch.
+ * No reference counterpart. */
+int64_t qd_kernel_table_names(char* buf, int64_t cap);
 
 /* Copies of the triage's iteration-1 tables (host-only graphs): lut[n_pad]
  * (bit b = column j's hard decision after min-sum iteration 1 under syndrome
