@@ -85,9 +85,9 @@ __device__ __forceinline__ double max_abs2_f64(double a, double b) {
 // compares) and the variable pass flips a message's sign by the sign bit of the
 // v2c message it sent.  Both differ from the compares only through zero
 // entries, and a zero entry makes the row's m1 zero, so a row with m1 == 0
-// (a wave-uniform branch, taken while the row is still in registers: equal
-// priors send an exact +0 in iteration 1, so every listed shot meets one in
-// iteration 2) takes the parity from the compares and gives m2 (the magnitude
+// (one wave-uniform branch after all check rounds, which reads the row again:
+// equal priors send an exact +0 in iteration 1, so every listed shot meets one
+// in iteration 2) takes the parity from the compares and gives m2 (the magnitude
 // its zero entries select) the sign that makes the variable side's sign bit
 // test exact: the parity, flipped when the zeros are +0.  A
 // row holding both +0 and -0 has m2 = 0, where only the sign of a zero message
@@ -121,8 +121,18 @@ __device__ __forceinline__ Top2 top2_tree(const double* v) {
     } else {
         constexpr int M = B + ((E - B) / 2 + 1) / 2 * 2;  // left part: an even count of leaves' values
         const Top2 a = top2_tree<B, M>(v);
-        const Top2 b = top2_tree<M, E>(v);
         Top2 r;
+        if constexpr (E - M == 1) {
+            // a single value on the right: |v[M]| as an operand modifier of the
+            // merge itself (the same operands, without a register pair for the leaf)
+            r.lo = min_abs_f64(a.lo, v[M]);
+            double h = max_abs_f64(a.lo, v[M]);
+            if (a.has_hi) h = min_f64(h, a.hi);
+            r.hi = h;
+            r.has_hi = true;
+            return r;
+        }
+        const Top2 b = top2_tree<M, E>(v);
         r.lo = min_f64(a.lo, b.lo);
         double h = max_f64(a.lo, b.lo);
         if (a.has_hi && b.has_hi)
@@ -271,67 +281,104 @@ struct MsCore {
             // ---- check pass: state (m1, m2) with the parity in both signs
             // (STATE0: iteration 1 starts from the table's state instead) ----
             if (!STATE0 || it != 1) {
-#pragma unroll
-                for (int rc = 0; rc < RC; ++rc) {
+                // three sweeps over a group of check rounds, so that no round's row
+                // loads wait behind another round's minima, branch or store
+                auto load_row = [&](int rc, T (&w)[kDR]) {
                     const int i = min(rc * 64 + lane, m);  // pad check lanes share the Big row m
-                    T v[kDR];
                     // odd f64 rows load only their DRC slots (r03i A/B: -0.5% BP kernel time)
-                    if constexpr (sizeof(T) == 8 && DRC % 2 == 1) lds_load_first<T, DRC>(v2c + i * DRS, v);
-                    else lds_load<T, kDR>(v2c + i * DRS, v);
-                    T m1 = Big<T>::v, m2 = Big<T>::v;
-                    bool par = sbit[rc];
-                    if constexpr (sizeof(T) == 4) {
+                    if constexpr (sizeof(T) == 8 && DRC % 2 == 1) lds_load_first<T, DRC>(v2c + i * DRS, w);
+                    else lds_load<T, kDR>(v2c + i * DRS, w);
+                };
+                // (a group is every round; four rounds go two at a time: four rows at
+                // once only add to the scratch of the (4, 9, 8) kernels)
+                constexpr int G = RC > 2 ? 2 : RC;
+                static_assert(RC % G == 0, "whole groups");
 #pragma unroll
-                        for (int k = 0; k < DRC; ++k) {
-                            const T av = fabs(v[k]);
-                            m2 = med3(av, m1, m2);
-                            m1 = med3(av, m1, -Big<T>::v);  // true median = min(|v|, m1): one VALU, abs modifier
+                for (int g0 = 0; g0 < RC; g0 += G) {
+                    // sweep 1: the group's rows
+                    T v[G][kDR];
+#pragma unroll
+                    for (int r = 0; r < G; ++r) load_row(g0 + r, v[r]);
+                    // sweep 2: minima, parity and state per round
+                    V2 s2[G];
+#pragma unroll
+                    for (int r = 0; r < G; ++r) {
+                        const int rc = g0 + r;
+                        T m1 = Big<T>::v, m2 = Big<T>::v;
+                        if constexpr (sizeof(T) == 4) {
+#pragma unroll
+                            for (int k = 0; k < DRC; ++k) {
+                                const T av = fabs(v[r][k]);
+                                m2 = med3(av, m1, m2);
+                                m1 = med3(av, m1, -Big<T>::v);  // true median = min(|v|, m1): one VALU, abs modifier
+                            }
+                        } else {
+                            // f64: (minimum, second minimum) of |v| by a merge tree instead of a
+                            // sequential chain (17 instead of 21 f64 ops for 7 values, depth 5
+                            // instead of 14); the same two values, so bit-identical
+                            const Top2 t = top2_tree<0, DRC>(v[r]);
+                            m1 = t.lo;
+                            m2 = t.hi;
                         }
-                    } else {
-                        // f64: (minimum, second minimum) of |v| by a merge tree instead of a
-                        // sequential chain (17 instead of 21 f64 ops for 7 values, depth 5
-                        // instead of 14); the same two values, so bit-identical
-                        const Top2 t = top2_tree<0, DRC>(v);
-                        m1 = t.lo;
-                        m2 = t.hi;
+                        if constexpr (SB) {
+                            // sign-canonical row: the parity is the XOR of the sign bits
+                            uint32_t hx = sbit[rc] ? 0x80000000u : 0u;
+                            int k = 0;
+#pragma unroll
+                            for (; k + 1 < DRC; k += 2)
+                                hx = __builtin_amdgcn_bitop3_b32(hx, f64_hi(v[r][k]), f64_hi(v[r][k + 1]), 0x96);
+                            if (k < DRC) hx ^= f64_hi(v[r][k]);
+                            // m1, m2 >= +0: the XOR of the parity bit sets their sign bit
+                            s2[r].x = f64_xor_sign(m1, hx);
+                            s2[r].y = f64_xor_sign(m2, hx);
+                        } else {
+                            bool par = sbit[rc];
+#pragma unroll
+                            for (int k = 0; k < DRC; ++k)
+                                par ^= v[r][k] <= (T)0;  // ldpc: bit_to_check <= 0 flips the sign (s_xor of compare masks)
+                            // both minima carry the parity in their sign bit (they are >= +0)
+                            s2[r].x = par ? -m1 : m1;
+                            s2[r].y = par ? -m2 : m2;
+                        }
                     }
-                    V2 s2;
+                    // sweep 3: the states
+#pragma unroll
+                    for (int r = 0; r < G; ++r) *reinterpret_cast<V2*>(st + 2 * sslot[g0 + r]) = s2[r];
                     if constexpr (SB) {
-                        // sign-canonical row: the parity is the XOR of the sign bits
-                        uint32_t hx = par ? 0x80000000u : 0u;
-                        int k = 0;
+                        // a row with a zero entry (one wave-uniform test for the group):
+                        // m1's sign is the parity by ldpc's compares; m2 (the magnitude the
+                        // row's zero entries select) gets the parity flipped when those zeros
+                        // are +0, so that the variable side's sign-bit test gives
+                        // parity ^ (v <= 0) for them too.  The rare branch reads its rows
+                        // again, one round at a time (nothing has written them since sweep 1:
+                        // holding sweep 1's rows for it costs the 3-waves-per-SIMD build its
+                        // register budget), and writes the state a second time (a state
+                        // patched in registers ahead of sweep 3 costs the loop four copies)
+                        bool zero = false;
 #pragma unroll
-                        for (; k + 1 < DRC; k += 2) hx = __builtin_amdgcn_bitop3_b32(hx, f64_hi(v[k]), f64_hi(v[k + 1]), 0x96);
-                        if (k < DRC) hx ^= f64_hi(v[k]);
-                        // m1, m2 >= +0: the XOR of the parity bit sets their sign bit
-                        s2.x = f64_xor_sign(m1, hx);
-                        s2.y = f64_xor_sign(m2, hx);
-                        // a row with a zero entry (wave-uniform test; the row is still in
-                        // registers): m1's sign is the parity by ldpc's compares; m2 (the
-                        // magnitude the row's zero entries select) gets the parity flipped
-                        // when those zeros are +0, so that the variable side's sign-bit
-                        // test gives parity ^ (v <= 0) for them too
-                        if (__ballot(s2.x == (T)0)) {
-                            if (s2.x == (T)0) {
-                                bool pz = false;
+                        for (int r = 0; r < G; ++r) zero |= s2[r].x == (T)0;
+                        if (__builtin_expect(__ballot(zero) != 0ull, 0)) {
+                            asm volatile("" ::: "memory");  // a load of its own, not sweep 1's registers
 #pragma unroll
-                                for (int j = 0; j < DRC; ++j) {
-                                    par ^= v[j] <= (T)0;
-                                    pz |= FBits<T>::to(v[j]) == 0;  // +0
+                            for (int r = 0; r < G; ++r) {
+                                const int rc = g0 + r;
+                                if (s2[r].x == (T)0) {
+                                    T w[kDR];
+                                    load_row(rc, w);
+                                    bool par = sbit[rc], pz = false;
+#pragma unroll
+                                    for (int j = 0; j < DRC; ++j) {
+                                        par ^= w[j] <= (T)0;
+                                        pz |= FBits<T>::to(w[j]) == 0;  // +0
+                                    }
+                                    V2 f;
+                                    f.x = par ? -(T)0 : (T)0;
+                                    f.y = (par != pz) ? -fabs(s2[r].y) : fabs(s2[r].y);
+                                    *reinterpret_cast<V2*>(st + 2 * sslot[rc]) = f;
                                 }
-                                s2.x = par ? -(T)0 : (T)0;
-                                s2.y = (par != pz) ? -fabs(s2.y) : fabs(s2.y);
                             }
                         }
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < DRC; ++k)
-                            par ^= v[k] <= (T)0;  // ldpc: bit_to_check <= 0 flips the sign (s_xor of compare masks)
-                        // both minima carry the parity in their sign bit (they are >= +0)
-                        s2.x = par ? -m1 : m1;
-                        s2.y = par ? -m2 : m2;
                     }
-                    *reinterpret_cast<V2*>(st + 2 * sslot[rc]) = s2;
                 }
                 wave_lds_sync();
             }
