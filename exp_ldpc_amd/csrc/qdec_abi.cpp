@@ -940,13 +940,12 @@ int qd_osd_batch_device_placed(qd_graph* G, int32_t method, int32_t order, int64
         if (B == 0) return;
         if (!llr || (!syn && !syn_flags)) throw Fail(-83, "null OSD inputs");
         if (llr_precision != QD_F32 && llr_precision != QD_F64) throw Fail(-84, "invalid llr precision");
-        const bool onchip = placement != QD_OSD_HBM && osd_kernel_supports(G->dg);
-        OsdHbmLayout L;
-        if (!onchip) {
+        OsdPlaced pl;
+        osd_place(G->dg, placement, &pl);
+        if (pl.kernel == kOsdNone) {
             if (placement == QD_OSD_ONCHIP)
                 throw Fail(-85, "graph too large for the device OSD (LDS image above 160 KiB)");
-            if (!osd_hbm_choose(G->dg, &L))
-                throw Fail(-48, "graph too large for the HBM OSD kernel (its LDS part above 160 KiB, or k > 256)");
+            throw Fail(-48, "graph too large for the HBM OSD kernel (its LDS part above 160 KiB, or k > 256)");
         }
         if (fail && G->dg.k > 256) throw Fail(-86, "fused failure check after OSD supports <= 256 logicals");
         if (G->host_only) throw Fail(-16, "host-only graph (qd_graph_create_host): no device to run OSD on");
@@ -967,10 +966,10 @@ int qd_osd_batch_device_placed(qd_graph* G, int32_t method, int32_t order, int64
         a.corr_out = corr_out;
         a.fail = fail;
         int rc;
-        if (onchip) {
+        if (pl.kernel != kOsdHbm) {
             rc = launch_osd(G->dg, a, G->num_cus, (hipStream_t)stream);
         } else {
-            const int64_t slots = osd_scratch_acquire(G, L, B, (hipStream_t)stream);
+            const int64_t slots = osd_scratch_acquire(G, pl.L, B, (hipStream_t)stream);
             rc = launch_osd_hbm(G->dg, a, G->osd_ws, slots, (hipStream_t)stream);
             osd_scratch_release(G, slots, (hipStream_t)stream);
         }
@@ -984,16 +983,16 @@ int qd_osd_kernel_info_placed(const qd_graph* G, int32_t placement, int64_t out[
         if (out) out[0] = out[1] = out[2] = out[3] = 0;
         check_osd_placement(placement);
         if (!G) return;
-        OsdChoice c{0, 0, 0};
-        if (placement != QD_OSD_HBM && osd_choose(G->dg, &c)) {
-            if (out) out[0] = c.rs ? 0 : 1, out[1] = c.rs, out[2] = c.w, out[3] = c.lds;
-            held = 1;
-            return;
-        }
-        OsdHbmLayout L;
-        if (placement == QD_OSD_ONCHIP || !osd_hbm_choose(G->dg, &L)) return;
-        if (out) out[0] = 2, out[1] = 0, out[2] = L.W, out[3] = L.slot_bytes;
+        OsdPlaced pl;
+        osd_place(G->dg, placement, &pl);
+        if (pl.kernel == kOsdNone) return;
         held = 1;
+        if (!out) return;
+        out[0] = pl.kernel;
+        if (pl.kernel == kOsdHbm)
+            out[1] = 0, out[2] = pl.L.W, out[3] = pl.L.slot_bytes;
+        else
+            out[1] = pl.c.rs, out[2] = pl.c.w, out[3] = pl.c.lds;
     });
     return rc != 0 ? rc : held;
 }

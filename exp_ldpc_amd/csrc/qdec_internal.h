@@ -132,6 +132,19 @@ struct OsdHbmLayout {
 bool osd_hbm_choose(const DevGraph& g, OsdHbmLayout* L);
 // `scratch` holds `slots` slots of L.slot_bytes; the grid is min(slots, B)
 int launch_osd_hbm(const DevGraph& g, const OsdArgs& a, void* scratch, int64_t slots, hipStream_t stream);
+// Which kernel runs a graph under a placement (QD_OSD_ONCHIP / _HBM / _AUTO of
+// qdec.h, checked by the caller): on chip where osd_choose holds the graph,
+// unless the HBM kernel is forced; otherwise the HBM kernel where
+// osd_hbm_choose holds it, unless on chip is forced.  The kernel's value is
+// what qd_osd_kernel_info_placed reports in out[0]; c is set for the two
+// on-chip kernels, L for the HBM kernel.  No HIP call.
+enum OsdKernel { kOsdNone = -1, kOsdRegister = 0, kOsdWorkgroup = 1, kOsdHbm = 2 };
+struct OsdPlaced {
+    OsdKernel kernel;
+    OsdChoice c;
+    OsdHbmLayout L;
+};
+void osd_place(const DevGraph& g, int placement, OsdPlaced* p);
 // slots per CU of the HBM kernel by default (DESIGN §3.6c has the sweep)
 constexpr int kOsdHbmSlotsPerCu = 8;
 

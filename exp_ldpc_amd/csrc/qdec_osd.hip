@@ -15,6 +15,11 @@
 //      first lambda; the candidate of least Hamming weight wins, an earlier
 //      candidate keeping a tie.
 //
+// The pieces that more than one kernel uses (key fill, bitonic compare-exchange,
+// syndrome bit, non-pivot list, search width, candidate key, pair index,
+// finalize) are in qdec_osd_steps.h, shared with osd_hbm_kernel
+// (qdec_osd_hbm.hip).  Steps 5 and 6 are each kernel's own text.
+//
 // One wave64 per shot (persistent over the batch).  Row i of the augmented
 // matrix [H_sorted | s] lives in registers of lane i % 64, slot i / 64 (RS <= 6
 // slots: m <= 384, i.e. spacetime graphs up to R = 2; W <= 16 64-bit words:
@@ -31,23 +36,16 @@
 #include "qdec_device.h"
 #include "qdec_internal.h"
 #include "qdec_kernels.h"
+#include "qdec_osd_steps.h"
 
 namespace qdec {
-
-constexpr int kOsdMaxLam = 64;  // pair / exhaustive search width kept in LDS
 
 // LDS layout of one wave (byte offsets); identical on host and device.
 struct OsdLayout {
     int ns, o_key, o_idx, o_pos, o_isp, o_piv, o_npv, o_red, o_tcl, o_out, total;
     __host__ __device__ OsdLayout(int n, int m, int RS, int W) {
-        ns = 64;
-        while (ns < n) ns <<= 1;
-        int o = 0;
-        auto take = [&](int bytes) {
-            const int at = o;
-            o += (bytes + 15) / 16 * 16;
-            return at;
-        };
+        ns = osd_sort_size(n);
+        OsdTake<int> take;
         o_key = take(8 * ns);
         o_red = take(8 * RS * 64 * W);
         o_tcl = take(8 * kOsdMaxLam * RS);
@@ -57,7 +55,7 @@ struct OsdLayout {
         o_npv = take(2 * n);
         o_isp = take(n);
         o_out = take(n);
-        total = o;
+        total = take.o;
         (void)RS;
     }
 };
@@ -66,14 +64,6 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
     return ((uint64_t)hi << 32) | lo;
-}
-
-// Ascending doubles -> ascending unsigned keys (-0.0 folded onto +0.0, as the
-// host's `<` comparison treats them as equal).
-__device__ __forceinline__ uint64_t order_key(double v) {
-    uint64_t b = (uint64_t)__double_as_longlong(v);
-    if (b == 0x8000000000000000ull) b = 0;
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 // Calls f(std::integral_constant<int, I>) for I = B .. E-1 (compile-time indices).
@@ -136,37 +126,9 @@ __global__ __launch_bounds__(64) void osd_wave_kernel(DevGraph g, OsdArgs a) {
     for (int64_t shot = blockIdx.x; shot < a.B; shot += gridDim.x) {
         if (a.status && (a.status[shot] & 1)) continue;  // BP converged: nothing to do
         // ---- 1. stable sort of the columns by log-probability ratio
-        for (int k = lane; k < NS; k += 64) {
-            uint64_t key = ~0ull;
-            uint16_t idx = 0xffff;
-            if (k < n) {
-                const double v = a.llr_f32 ? (double)static_cast<const float*>(a.llr)[shot * n + k]
-                                           : static_cast<const double*>(a.llr)[shot * n + k];
-                key = order_key(v);
-                idx = (uint16_t)k;
-            }
-            skey[k] = key;
-            sidx[k] = idx;
-        }
+        osd_fill_keys(a, shot, n, NS, skey, sidx, lane, 64);
         __syncthreads();
-        for (int size = 2; size <= NS; size <<= 1) {
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int t = lane; t < NS / 2; t += 64) {
-                    const int i = 2 * t - (t & (stride - 1));
-                    const int j = i + stride;
-                    const uint64_t ki = skey[i], kj = skey[j];
-                    const uint16_t ii = sidx[i], ij = sidx[j];
-                    const bool gt = ki > kj || (ki == kj && ii > ij);
-                    if (gt == ((i & size) == 0)) {
-                        skey[i] = kj;
-                        skey[j] = ki;
-                        sidx[i] = ij;
-                        sidx[j] = ii;
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        bitonic_sort_lds(skey, sidx, NS, lane, 64);
         for (int k = lane; k < n; k += 64) {
             pos[sidx[k]] = (uint16_t)k;
             isp[k] = 0;
@@ -181,14 +143,11 @@ __global__ __launch_bounds__(64) void osd_wave_kernel(DevGraph g, OsdArgs a) {
             for (int w = 0; w < W; ++w) row[s][w] = 0;
             const int i = s * 64 + lane;
             if (i < m) {
-                int sb = a.syn ? (a.syn[shot * m + i] & 1) : 0;
+                int sb = osd_syn_bit(a, shot, m, i);
                 for (int e = rp[i]; e < rp[i + 1]; ++e) {
                     const int j = ci[e];
                     flip_bit<W>(row[s], pos[j]);
-                    if (a.syn_flags && j < g.n_data) {
-                        if ((a.syn_flags & 1) && a.base) sb ^= a.base[shot * g.n_data + j] & 1;
-                        if ((a.syn_flags & 2) && a.readout) sb ^= a.readout[shot * g.n_data + j] & 1;
-                    }
+                    sb ^= osd_syn_term(g, a, shot, j);
                 }
                 if (sb) flip_bit<W>(row[s], n);
             }
@@ -264,14 +223,7 @@ __global__ __launch_bounds__(64) void osd_wave_kernel(DevGraph g, OsdArgs a) {
             x0[s] = __ballot(i < rank && get_bit<W>(row[s], n));
         }
         __syncthreads();
-        int kn = 0;
-        for (int base = 0; base < n; base += 64) {
-            const int k = base + lane;
-            const bool f = k < n && !isp[k];
-            const uint64_t bal = __ballot(f);
-            if (f) npv[kn + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)k;
-            kn += __popcll(bal);
-        }
+        const int kn = osd_nonpivots(isp, n, npv, n, lane);
         __syncthreads();
         auto tcol = [&](int k, uint64_t (&tc)[RS]) {
             const int w = k >> 6, b = k & 63;
@@ -281,8 +233,7 @@ __global__ __launch_bounds__(64) void osd_wave_kernel(DevGraph g, OsdArgs a) {
                 tc[s] = __ballot(i < rank && ((red[(size_t)i * W + w] >> b) & 1));
             }
         };
-        const int lam = a.order < 0 ? 0 : (a.order < kn ? a.order : kn);
-        const int lam_s = lam < kOsdMaxLam ? lam : kOsdMaxLam;
+        const int lam_s = osd_lam(a, kn);
         for (int t = 0; t < lam_s; ++t) {
             uint64_t tc[RS];
             tcol(npv[t], tc);
@@ -392,14 +343,7 @@ __global__ __launch_bounds__(64) void osd_wave_kernel(DevGraph g, OsdArgs a) {
                     for (int s = 0; s < RS; ++s) xp[s] ^= tcl[t * RS + s];
         }
         emit(xp, kind);
-        DecodeArgs fa{};
-        fa.B = a.B;
-        fa.base = a.base;
-        fa.readout = a.readout;
-        fa.x_out = a.osdw_out;
-        fa.corr_out = a.corr_out;
-        fa.fail = a.fail;
-        finalize_shot(g, fa, shot, outb, false, false, 0, lane);
+        osd_finalize(g, a, shot, outb, lane);
         __syncthreads();
     }
 }
@@ -414,22 +358,16 @@ __global__ __launch_bounds__(64) void osd_wave_kernel(DevGraph g, OsdArgs a) {
 // (LDS atomic min), row swap, then the rows holding the pivot bit (flags taken
 // before any write) XOR the pivot row, over (row, word) pairs.  Candidate
 // weights are computed thread-parallel and the winner is the minimum of
-// (weight, position in the host's candidate order).
+// (weight, place in the host's candidate order): osd_key, qdec_osd_steps.h.
 constexpr int kOsdBlock = 256;
 
 struct OsdBlockLayout {
     int ns, W, RW, o_rows, o_key, o_idx, o_pos, o_piv, o_npv, o_isp, o_out, o_hit, o_x0, o_tcl, o_ctl, total;
     __host__ __device__ OsdBlockLayout(int n, int m) {
-        ns = 64;
-        while (ns < n) ns <<= 1;
+        ns = osd_sort_size(n);
         W = (n + 1 + 63) / 64;
         RW = (m + 63) / 64;
-        int o = 0;
-        auto take = [&](int bytes) {
-            const int at = o;
-            o += (bytes + 15) / 16 * 16;
-            return at;
-        };
+        OsdTake<int> take;
         o_rows = take(8 * m * W);
         o_key = take(8 * ns);
         o_x0 = take(8 * RW);
@@ -442,7 +380,7 @@ struct OsdBlockLayout {
         o_isp = take(n);
         o_out = take(n);
         o_hit = take(m);
-        total = o;
+        total = take.o;
     }
 };
 
@@ -471,37 +409,9 @@ __global__ __launch_bounds__(kOsdBlock) void osd_block_kernel(DevGraph g, OsdArg
     for (int64_t shot = blockIdx.x; shot < a.B; shot += gridDim.x) {
         if (a.status && (a.status[shot] & 1)) continue;  // uniform over the workgroup
         // ---- 1. stable sort of the columns by log-probability ratio
-        for (int k = tid; k < NS; k += kOsdBlock) {
-            uint64_t key = ~0ull;
-            uint16_t idx = 0xffff;
-            if (k < n) {
-                const double v = a.llr_f32 ? (double)static_cast<const float*>(a.llr)[shot * n + k]
-                                           : static_cast<const double*>(a.llr)[shot * n + k];
-                key = order_key(v);
-                idx = (uint16_t)k;
-            }
-            skey[k] = key;
-            sidx[k] = idx;
-        }
+        osd_fill_keys(a, shot, n, NS, skey, sidx, tid, kOsdBlock);
         __syncthreads();
-        for (int size = 2; size <= NS; size <<= 1) {
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int t = tid; t < NS / 2; t += kOsdBlock) {
-                    const int i = 2 * t - (t & (stride - 1));
-                    const int j = i + stride;
-                    const uint64_t ki = skey[i], kj = skey[j];
-                    const uint16_t ii = sidx[i], ij = sidx[j];
-                    const bool gt = ki > kj || (ki == kj && ii > ij);
-                    if (gt == ((i & size) == 0)) {
-                        skey[i] = kj;
-                        skey[j] = ki;
-                        sidx[i] = ij;
-                        sidx[j] = ii;
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        bitonic_sort_lds(skey, sidx, NS, tid, kOsdBlock);
         for (int k = tid; k < n; k += kOsdBlock) {
             pos[sidx[k]] = (uint16_t)k;
             isp[k] = 0;
@@ -512,15 +422,12 @@ __global__ __launch_bounds__(kOsdBlock) void osd_block_kernel(DevGraph g, OsdArg
         // ---- 2. augmented rows [H_sorted | s] (one thread per row)
         for (int i = tid; i < m; i += kOsdBlock) {
             uint64_t* r = A + (size_t)i * W;
-            int sb = a.syn ? (a.syn[shot * m + i] & 1) : 0;
+            int sb = osd_syn_bit(a, shot, m, i);
             for (int e = rp[i]; e < rp[i + 1]; ++e) {
                 const int j = ci[e];
                 const int k = pos[j];
                 r[k >> 6] ^= 1ull << (k & 63);
-                if (a.syn_flags && j < g.n_data) {
-                    if ((a.syn_flags & 1) && a.base) sb ^= a.base[shot * g.n_data + j] & 1;
-                    if ((a.syn_flags & 2) && a.readout) sb ^= a.readout[shot * g.n_data + j] & 1;
-                }
+                sb ^= osd_syn_term(g, a, shot, j);
             }
             if (sb) r[n >> 6] ^= 1ull << (n & 63);
         }
@@ -566,72 +473,46 @@ __global__ __launch_bounds__(kOsdBlock) void osd_block_kernel(DevGraph g, OsdArg
         }
 
         // ---- 4. transformed syndrome, non-pivot columns, the first lam transformed columns
-        for (int w = tid; w < RW; w += kOsdBlock) {
-            uint64_t v = 0;
-            for (int b = 0; b < 64; ++b) {
-                const int i = w * 64 + b;
-                if (i < rank && bit(i, n)) v |= 1ull << b;
-            }
-            x0[w] = v;
-        }
-        if (wave == 0) {
-            int kn = 0;
-            for (int base = 0; base < n; base += 64) {
-                const int k = base + lane;
-                const bool f = k < n && !isp[k];
-                const uint64_t bal = __ballot(f);
-                if (f) npv[kn + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)k;
-                kn += __popcll(bal);
-            }
-            if (lane == 0) ctl[2] = (unsigned long long)kn;
-        }
-        __syncthreads();
-        const int kn = (int)ctl[2];
-        const int lam = a.order < 0 ? 0 : (a.order < kn ? a.order : kn);
-        const int lam_s = lam < kOsdMaxLam ? lam : kOsdMaxLam;
-        for (int e = tid; e < lam_s * RW; e += kOsdBlock) {
-            const int t = e / RW, w = e % RW, k = npv[t];
+        auto colword = [&](int k, int w) {  // rows 64 w .. 64 w + 63 of transformed column k
             uint64_t v = 0;
             for (int b = 0; b < 64; ++b) {
                 const int i = w * 64 + b;
                 if (i < rank && bit(i, k)) v |= 1ull << b;
             }
-            tcl[t * RW + w] = v;
+            return v;
+        };
+        for (int w = tid; w < RW; w += kOsdBlock) x0[w] = colword(n, w);
+        if (wave == 0) {
+            const int found = osd_nonpivots(isp, n, npv, n, lane);
+            if (lane == 0) ctl[2] = (unsigned long long)found;
         }
+        __syncthreads();
+        const int kn = (int)ctl[2];
+        const int lam_s = osd_lam(a, kn);
+        for (int e = tid; e < lam_s * RW; e += kOsdBlock) tcl[e] = colword(npv[e / RW], e % RW);
         int w0 = 0;
         for (int w = 0; w < RW; ++w) w0 += __popcll(x0[w]);
-        if (tid == 0) ctl[1] = ((unsigned long long)w0 << 32);  // OSD-0: weight, order 0
+        if (tid == 0) ctl[1] = osd_key(w0, 0);  // OSD-0: weight, place 0
         __syncthreads();
 
-        // ---- 5. candidates: key = weight << 32 | position in the host's order
-        // (1 + t: single t, 1 + kn + pair index, or the OSD-E mask)
+        // ---- 5. candidates: osd_key(weight, place in the host's order), the place
+        // 1 + t for single t, 1 + kn + pair index, or the OSD-E mask
         unsigned long long best = ~0ull;
         if (a.method == 2) {
             for (int t = tid; t < kn; t += kOsdBlock) {
                 const int k = npv[t];
                 int wgt = 1;
-                for (int w = 0; w < RW; ++w) {
-                    uint64_t v = 0;
-                    for (int b = 0; b < 64; ++b) {
-                        const int i = w * 64 + b;
-                        if (i < rank && bit(i, k)) v |= 1ull << b;
-                    }
-                    wgt += __popcll(x0[w] ^ v);
-                }
-                const unsigned long long key = ((unsigned long long)wgt << 32) | (unsigned long long)(1 + t);
+                for (int w = 0; w < RW; ++w) wgt += __popcll(x0[w] ^ colword(k, w));
+                const unsigned long long key = osd_key(wgt, (uint32_t)(1 + t));
                 best = key < best ? key : best;
             }
             const int np = lam_s * (lam_s - 1) / 2;
             for (int q = tid; q < np; q += kOsdBlock) {
-                int u = 0, rem = q;  // q -> (u, v), u < v, lexicographic
-                while (rem >= lam_s - 1 - u) {
-                    rem -= lam_s - 1 - u;
-                    ++u;
-                }
-                const int v = u + 1 + rem;
+                int u, v;
+                pair_of(q, lam_s, u, v);
                 int wgt = 2;
                 for (int w = 0; w < RW; ++w) wgt += __popcll(x0[w] ^ tcl[u * RW + w] ^ tcl[v * RW + w]);
-                const unsigned long long key = ((unsigned long long)wgt << 32) | (unsigned long long)(1 + kn + q);
+                const unsigned long long key = osd_key(wgt, (uint32_t)(1 + kn + q));
                 best = key < best ? key : best;
             }
         } else if (a.method == 1 && lam_s > 0) {
@@ -644,35 +525,26 @@ __global__ __launch_bounds__(kOsdBlock) void osd_block_kernel(DevGraph g, OsdArg
                         if ((sm >> t) & 1) c ^= tcl[t * RW + w];
                     wgt += __popcll(c);
                 }
-                const unsigned long long key = ((unsigned long long)wgt << 32) | sm;
+                const unsigned long long key = osd_key(wgt, sm);
                 best = key < best ? key : best;
             }
         }
-        // OSD-0 keeps a tie (strict improvement): its key has the lowest position
+        // OSD-0 keeps a tie (strict improvement): its key has the lowest place
         if (best != ~0ull) atomicMin(&ctl[1], best);
         __syncthreads();
-        const unsigned long long bk = ctl[1];
-        const int bpos = (int)(bk & 0xffffffffu);
+        const int bpos = (int)(ctl[1] & 0xffffffffu);
         int kind = 0, ca = -1, cb = -1;
         uint32_t cmask = 0;
         if (bpos != 0) {
-            if (a.method == 2) {
-                if (bpos <= kn) {
-                    kind = 1;
-                    ca = bpos - 1;
-                } else {
-                    int q = bpos - 1 - kn, u = 0;
-                    while (q >= lam_s - 1 - u) {
-                        q -= lam_s - 1 - u;
-                        ++u;
-                    }
-                    kind = 2;
-                    ca = u;
-                    cb = u + 1 + q;
-                }
-            } else {
+            if (a.method != 2) {
                 kind = 3;
                 cmask = (uint32_t)bpos;
+            } else if (bpos <= kn) {
+                kind = 1;
+                ca = bpos - 1;
+            } else {
+                kind = 2;
+                pair_of(bpos - 1 - kn, lam_s, ca, cb);
             }
         }
 
@@ -708,16 +580,7 @@ __global__ __launch_bounds__(kOsdBlock) void osd_block_kernel(DevGraph g, OsdArg
             __syncthreads();
         }
         emit(kind);
-        if (wave == 0) {
-            DecodeArgs fa{};
-            fa.B = a.B;
-            fa.base = a.base;
-            fa.readout = a.readout;
-            fa.x_out = a.osdw_out;
-            fa.corr_out = a.corr_out;
-            fa.fail = a.fail;
-            finalize_shot(g, fa, shot, outb, false, false, 0, lane);
-        }
+        if (wave == 0) osd_finalize(g, a, shot, outb, lane);
         __syncthreads();
     }
 }

@@ -1,8 +1,14 @@
 // qdec_osd_hbm.hip -- the OSD stage (steps 1-6 at the top of qdec_osd.hip) for
 // graphs whose augmented rows do not fit a CU's LDS: circuit detector error
-// models (648 x 25,684 at R = 3: 2 MiB of rows), deep spacetime graphs.  Same
-// spec, tie rules and outputs as osd_block_kernel and the host stage; the result
-// is bit-identical to qd_osd_batch.
+// models (648 x 25,684 at R = 3: 2 MiB of rows), deep spacetime graphs.  The
+// steps it has in common with the on-chip kernels, and with them every tie rule,
+// come from qdec_osd_steps.h (key fill, compare-exchange, syndrome bit,
+// non-pivot list, search width, candidate key, pair index, finalize); the result
+// is bit-identical to qd_osd_batch.  Its own: the slot, the chunked sort driver,
+// the elimination, and steps 5 and 6 (candidate search, pick, outputs), which
+// osd_block_kernel also has in its own text: shared through the header they
+// cost this kernel 1 % on the 432 x 1224 graph.  A change to the
+// candidate order or to emit is made in both workgroup kernels.
 //
 // One 256-thread workgroup per BP-unconverged shot, persistent over the batch.
 // Workgroup b owns slot b of a scratch the graph handle owns (qdec_abi.cpp) and
@@ -34,9 +40,11 @@
 //             gathered bit by bit and no transposed copy is kept
 #include <hip/hip_runtime.h>
 
+#include "../../include/qdec.h"
 #include "qdec_device.h"
 #include "qdec_internal.h"
 #include "qdec_kernels.h"
+#include "qdec_osd_steps.h"
 
 namespace qdec {
 
@@ -44,14 +52,7 @@ namespace {
 
 constexpr int kHbmBlock = 256;
 constexpr int kHbmWaves = kHbmBlock / 64;
-constexpr int kHbmMaxLam = 64;      // pair / exhaustive search width kept in LDS
 constexpr int kHbmSortChunk = 2048; // keys sorted in LDS at a time
-
-__device__ __forceinline__ uint64_t hbm_order_key(double v) {
-    uint64_t b = (uint64_t)__double_as_longlong(v);
-    if (b == 0x8000000000000000ull) b = 0;
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 __device__ __forceinline__ uint32_t readlane32(uint32_t v, int l) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
@@ -61,16 +62,10 @@ __device__ __forceinline__ uint32_t readlane32(uint32_t v, int l) {
 
 // Slot and LDS layouts (byte offsets); identical on host and device.
 OsdHbmLayout::OsdHbmLayout(int64_t n, int64_t m) {
-    ns = 64;
-    while (ns < n) ns <<= 1;
+    ns = osd_sort_size(n);
     W = (n + 1 + 63) / 64;
     RW = (m + 63) / 64;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t at = o;
-        o += (bytes + 15) / 16 * 16;
-        return at;
-    };
+    OsdTake<int64_t> take;
     s_rows = take(8 * m * W);
     s_key = take(8 * ns);
     s_idx = take(4 * ns);
@@ -78,19 +73,19 @@ OsdHbmLayout::OsdHbmLayout(int64_t n, int64_t m) {
     s_piv = take(4 * (m > 0 ? m : 1));
     s_isp = take(n);
     s_out = take(n);
-    slot_bytes = (o + 255) / 256 * 256;
-    o = 0;
+    slot_bytes = (take.o + 255) / 256 * 256;
+    take.o = 0;
     l_ctl = take(64);
-    l_npv = take(4 * kHbmMaxLam);
+    l_npv = take(4 * kOsdMaxLam);
     l_x0 = take(8 * RW);
-    l_tcl = take(8 * kHbmMaxLam * RW);
+    l_tcl = take(8 * kOsdMaxLam * RW);
     l_row = take(8 * kHbmWaves * W);
     l_hit = take(m);
     const int64_t chunk = ns < kHbmSortChunk ? ns : kHbmSortChunk;
     l_skey = 0;  // the sort's chunk overlays everything above
     l_sidx = 8 * chunk;
     const int64_t sort_bytes = 12 * chunk;
-    lds_bytes = o > sort_bytes ? o : sort_bytes;
+    lds_bytes = take.o > sort_bytes ? take.o : sort_bytes;
 }
 
 __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs a, unsigned char* scratch,
@@ -131,19 +126,7 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
             for (int size = lo; size <= hi; size <<= 1) {
                 const int s0 = (size >> 1) < (CH >> 1) ? (size >> 1) : (CH >> 1);
                 for (int stride = s0; stride > 0; stride >>= 1) {
-                    for (int t = tid; t < CH / 2; t += kHbmBlock) {
-                        const int i = 2 * t - (t & (stride - 1));
-                        const int j = i + stride;
-                        const uint64_t ki = lkey[i], kj = lkey[j];
-                        const uint32_t ii = lidx[i], ij = lidx[j];
-                        const bool gt = ki > kj || (ki == kj && ii > ij);
-                        if (gt == (((c0 + i) & size) == 0)) {
-                            lkey[i] = kj;
-                            lkey[j] = ki;
-                            lidx[i] = ij;
-                            lidx[j] = ii;
-                        }
-                    }
+                    bitonic_pass(lkey, lidx, CH, size, stride, c0, tid, kHbmBlock);
                     __syncthreads();
                 }
             }
@@ -158,35 +141,12 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
     for (int64_t shot = blockIdx.x; shot < a.B; shot += gridDim.x) {
         if (a.status && (a.status[shot] & 1)) continue;  // uniform over the workgroup
         // ---- 1. stable sort of the columns by log-probability ratio
-        for (int k = tid; k < NS; k += kHbmBlock) {
-            uint64_t key = ~0ull;
-            uint32_t idx = 0xffffffffu;
-            if (k < n) {
-                const double v = a.llr_f32 ? (double)static_cast<const float*>(a.llr)[shot * n + k]
-                                           : static_cast<const double*>(a.llr)[shot * n + k];
-                key = hbm_order_key(v);
-                idx = (uint32_t)k;
-            }
-            gkey[k] = key;
-            sidx[k] = idx;
-        }
+        osd_fill_keys(a, shot, n, NS, gkey, sidx, tid, kHbmBlock);
         __syncthreads();
         sort_local(2, CH);
         for (int size = 2 * CH; size <= NS && size > 0; size <<= 1) {
             for (int stride = size >> 1; stride >= CH; stride >>= 1) {
-                for (int t = tid; t < NS / 2; t += kHbmBlock) {
-                    const int i = 2 * t - (t & (stride - 1));
-                    const int j = i + stride;
-                    const uint64_t ki = gkey[i], kj = gkey[j];
-                    const uint32_t ii = sidx[i], ij = sidx[j];
-                    const bool gt = ki > kj || (ki == kj && ii > ij);
-                    if (gt == ((i & size) == 0)) {
-                        gkey[i] = kj;
-                        gkey[j] = ki;
-                        sidx[i] = ij;
-                        sidx[j] = ii;
-                    }
-                }
+                bitonic_pass(gkey, sidx, NS, size, stride, 0, tid, kHbmBlock);
                 __syncthreads();
             }
             sort_local(size, size);
@@ -204,16 +164,13 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
             for (int i = wave; i < m; i += kHbmWaves) {
                 for (int w = lane; w < W; w += 64) rb[w] = 0;
                 __builtin_amdgcn_wave_barrier();  // one wave: LDS operations complete in order
-                int sb = (lane == 0 && a.syn) ? (a.syn[shot * m + i] & 1) : 0;
+                int sb = lane == 0 ? osd_syn_bit(a, shot, m, i) : 0;
                 for (int e = rp[i] + lane; e < rp[i + 1]; e += 64) {
                     const int j = ci[e];
                     const uint32_t k = pos[j];
                     if (k >= (uint32_t)n) continue;
                     atomicXor(reinterpret_cast<unsigned long long*>(&rb[k >> 6]), 1ull << (k & 63));
-                    if (a.syn_flags && j < g.n_data) {
-                        if ((a.syn_flags & 1) && a.base) sb ^= a.base[shot * g.n_data + j] & 1;
-                        if ((a.syn_flags & 2) && a.readout) sb ^= a.readout[shot * g.n_data + j] & 1;
-                    }
+                    sb ^= osd_syn_term(g, a, shot, j);
                 }
                 const int par = __popcll(__ballot(sb & 1)) & 1;
                 if (lane == 0 && par) atomicXor(reinterpret_cast<unsigned long long*>(&rb[n >> 6]), 1ull << (n & 63));
@@ -294,21 +251,10 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
 
         // ---- 4. transformed syndrome, the first lam non-pivot positions and their columns
         const int kn = n - rank;
-        const int lam = a.order < 0 ? 0 : (a.order < kn ? a.order : kn);
-        const int lam_s = lam < kHbmMaxLam ? lam : kHbmMaxLam;
+        const int lam_s = osd_lam(a, kn);
         for (int w = tid; w < RW; w += kHbmBlock) x0[w] = 0;
         for (int e = tid; e < lam_s * RW; e += kHbmBlock) tcl[e] = 0;
-        if (wave == 0) {
-            int found = 0;
-            for (int base = 0; base < n && found < lam_s; base += 64) {
-                const int k = base + lane;
-                const bool f = k < n && !isp[k];
-                const uint64_t bal = __ballot(f);
-                const int at = found + __popcll(bal & ((1ull << lane) - 1ull));
-                if (f && at < kHbmMaxLam) npv[at] = (uint32_t)k;
-                found += __popcll(bal);
-            }
-        }
+        if (wave == 0) osd_nonpivots(isp, n, npv, lam_s, lane);
         __syncthreads();
         for (int i = tid; i < rank; i += kHbmBlock)
             if (bit(i, n)) atomicOr(reinterpret_cast<unsigned long long*>(&x0[i >> 6]), 1ull << (i & 63));
@@ -320,12 +266,12 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
         __syncthreads();
         int w0 = 0;
         for (int w = 0; w < RW; ++w) w0 += __popcll(x0[w]);
-        if (tid == 0) ctl[1] = ((unsigned long long)w0 << 32);  // OSD-0: weight, order 0
+        if (tid == 0) ctl[1] = osd_key(w0, 0);  // OSD-0: weight, place 0
         __syncthreads();
 
-        // ---- 5. candidates: key = weight << 32 | place in the host's order
-        // (1 + k: the single at position k -- ascending in k as the host's walk of
-        // the non-pivot columns is; 1 + n + pair index; or the OSD-E mask)
+        // ---- 5. candidates: osd_key(weight, place in the host's order), the place
+        // 1 + k for the single at position k (ascending in k as the host's walk of
+        // the non-pivot columns is), 1 + n + pair index, or the OSD-E mask
         unsigned long long best = ~0ull;
         if (a.method == 2) {
             const int rwr = (rank + 63) / 64;
@@ -349,22 +295,17 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
                     }
                 }
                 if (valid) {
-                    const unsigned long long key = ((unsigned long long)wgt << 32) | (unsigned long long)(1u + (unsigned)k);
+                    const unsigned long long key = osd_key(wgt, 1u + (unsigned)k);
                     best = key < best ? key : best;
                 }
             }
             const int np = lam_s * (lam_s - 1) / 2;
             for (int q = tid; q < np; q += kHbmBlock) {
-                int u = 0, rem = q;  // q -> (u, v), u < v, lexicographic
-                while (rem >= lam_s - 1 - u) {
-                    rem -= lam_s - 1 - u;
-                    ++u;
-                }
-                const int v = u + 1 + rem;
+                int u, v;
+                pair_of(q, lam_s, u, v);
                 int wgt = 2;
                 for (int w = 0; w < RW; ++w) wgt += __popcll(x0[w] ^ tcl[u * RW + w] ^ tcl[v * RW + w]);
-                const unsigned long long key =
-                    ((unsigned long long)wgt << 32) | (unsigned long long)(1u + (unsigned)n + (unsigned)q);
+                const unsigned long long key = osd_key(wgt, 1u + (unsigned)n + (unsigned)q);
                 best = key < best ? key : best;
             }
         } else if (a.method == 1 && lam_s > 0) {
@@ -377,7 +318,7 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
                         if ((sm >> t) & 1) c ^= tcl[t * RW + w];
                     wgt += __popcll(c);
                 }
-                const unsigned long long key = ((unsigned long long)wgt << 32) | sm;
+                const unsigned long long key = osd_key(wgt, sm);
                 best = key < best ? key : best;
             }
         }
@@ -389,23 +330,15 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
         int kind = 0, ca = -1, cb = -1;  // kind 1: ca = the position; kind 2: ca, cb index npv
         uint32_t cmask = 0;
         if (bpos != 0) {
-            if (a.method == 2) {
-                if (bpos <= (uint32_t)n) {
-                    kind = 1;
-                    ca = (int)(bpos - 1);
-                } else {
-                    int q = (int)(bpos - 1 - (uint32_t)n), u = 0;
-                    while (q >= lam_s - 1 - u) {
-                        q -= lam_s - 1 - u;
-                        ++u;
-                    }
-                    kind = 2;
-                    ca = u;
-                    cb = u + 1 + q;
-                }
-            } else {
+            if (a.method != 2) {
                 kind = 3;
                 cmask = bpos;
+            } else if (bpos <= (uint32_t)n) {
+                kind = 1;
+                ca = (int)(bpos - 1);
+            } else {
+                kind = 2;
+                pair_of((int)(bpos - 1 - (uint32_t)n), lam_s, ca, cb);
             }
         }
 
@@ -446,16 +379,7 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
             __syncthreads();
         }
         emit(kind);
-        if (wave == 0) {
-            DecodeArgs fa{};
-            fa.B = a.B;
-            fa.base = a.base;
-            fa.readout = a.readout;
-            fa.x_out = a.osdw_out;
-            fa.corr_out = a.corr_out;
-            fa.fail = a.fail;
-            finalize_shot(g, fa, shot, outb, false, false, 0, lane);
-        }
+        if (wave == 0) osd_finalize(g, a, shot, outb, lane);
         __syncthreads();
     }
 }
@@ -465,9 +389,18 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
 // one CU and the fused failure check keeps its k <= 256 limit.
 bool osd_hbm_choose(const DevGraph& g, OsdHbmLayout* L) {
     if (g.m <= 0 || g.n <= 0 || g.k > 256) return false;
-    if ((int64_t)g.n + 1 + kHbmMaxLam * 32 >= (1ll << 31)) return false;
+    if ((int64_t)g.n + 1 + kOsdMaxLam * 32 >= (1ll << 31)) return false;
     *L = OsdHbmLayout(g.n, g.m);
     return L->lds_bytes <= 160 * 1024;
+}
+
+// The one place that turns a placement into a kernel (qdec_internal.h has the rule).
+void osd_place(const DevGraph& g, int placement, OsdPlaced* p) {
+    *p = OsdPlaced{kOsdNone, OsdChoice{0, 0, 0}, OsdHbmLayout()};
+    if (placement != QD_OSD_HBM && osd_choose(g, &p->c))
+        p->kernel = p->c.rs ? kOsdRegister : kOsdWorkgroup;
+    else if (placement != QD_OSD_ONCHIP && osd_hbm_choose(g, &p->L))
+        p->kernel = kOsdHbm;
 }
 
 int launch_osd_hbm(const DevGraph& g, const OsdArgs& a, void* scratch, int64_t slots, hipStream_t stream) {
