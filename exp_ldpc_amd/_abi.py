@@ -79,6 +79,10 @@ SIGNATURES = {
     "qd_circuit_create_host": (_i32, [_i32, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p, C.POINTER(_p)]),
     "qd_circuit_create_placed": (_i32, [_i32, _i32, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p, C.POINTER(_p)]),
     "qd_circuit_create_host_placed": (_i32, [_i32, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p, C.POINTER(_p)]),
+    "qd_circuit_create_args": (_i32, [_i32, _i32, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _p,
+                                      C.POINTER(_p)]),
+    "qd_circuit_create_host_args": (_i32, [_i32, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _p,
+                                           C.POINTER(_p)]),
     "qd_circuit_set_frame_slots": (_i32, [_p, _i64]),
     "qd_circuit_frame_info": (_i32, [_p, _p]),
     "qd_circuit_op_flags_copy": (_i32, [_p, _p]),

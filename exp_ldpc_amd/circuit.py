@@ -6,6 +6,9 @@ storage circuits (``python/qldpc/storage_sim.py:110-199``) and noise rewriters
 ``CompiledCircuit``: flat integer arrays the C ABI takes (``qd_circuit_create``,
 include/qdec.h), one probability / u32 threshold per instruction, and the
 detector and observable rows as CSR matrices over absolute record indices.
+``PAULI_CHANNEL_1(px, py, pz)`` and ``PAULI_CHANNEL_2(15 probabilities, Stim's
+order IX .. ZZ)`` keep their arguments in ``CompiledCircuit.args``; their entry
+of ``probs`` is the sum (``qd_circuit_create_args``).
 
 Stim applies an instruction's targets in order.  The compiler splits every gate,
 reset and measurement instruction into groups whose qubits are pairwise
@@ -30,12 +33,14 @@ import numpy as np
 import scipy.sparse as sp
 
 __all__ = ["CompiledCircuit", "Instruction", "ParsedCircuit", "compile_circuit", "parse", "bern_threshold",
-           "SUPPORTED", "OPCODES", "INVERT", "MAX_GROUPS", "LDS_LIMIT", "FRAME_PLACEMENTS"]
+           "SUPPORTED", "OPCODES", "CHANNEL_ARGS", "INVERT", "MAX_GROUPS", "LDS_LIMIT", "FRAME_PLACEMENTS"]
 
-OP_H, OP_CX, OP_CZ, OP_R, OP_RX, OP_M, OP_MX, OP_XERR, OP_YERR, OP_ZERR, OP_DEP1, OP_DEP2 = range(12)
+OP_H, OP_CX, OP_CZ, OP_R, OP_RX, OP_M, OP_MX, OP_XERR, OP_YERR, OP_ZERR, OP_DEP1, OP_DEP2, OP_PC1, OP_PC2 = range(14)
 OPCODES = {"H": OP_H, "CX": OP_CX, "CZ": OP_CZ, "R": OP_R, "RX": OP_RX, "M": OP_M, "MX": OP_MX,
            "X_ERROR": OP_XERR, "Y_ERROR": OP_YERR, "Z_ERROR": OP_ZERR, "DEPOLARIZE1": OP_DEP1,
-           "DEPOLARIZE2": OP_DEP2}
+           "DEPOLARIZE2": OP_DEP2, "PAULI_CHANNEL_1": OP_PC1, "PAULI_CHANNEL_2": OP_PC2}
+# noise instructions with one probability per outcome: name -> argument count
+CHANNEL_ARGS = {"PAULI_CHANNEL_1": 3, "PAULI_CHANNEL_2": 15}
 INVERT = 1 << 30       # measurement target bit: record inverted
 MAX_GROUPS = 4
 LDS_LIMIT = 160 * 1024
@@ -47,9 +52,9 @@ _ALIAS = {"RZ": "R", "MZ": "M", "MRZ": "MR", "CNOT": "CX"}
 _RESETS = ("R", "RX")
 _MEASURES = ("M", "MX", "MR", "MRX")
 _GATES = ("H", "CX", "CZ")
-_NOISE = ("X_ERROR", "Y_ERROR", "Z_ERROR", "DEPOLARIZE1", "DEPOLARIZE2")
+_NOISE = ("X_ERROR", "Y_ERROR", "Z_ERROR", "DEPOLARIZE1", "DEPOLARIZE2", "PAULI_CHANNEL_1", "PAULI_CHANNEL_2")
 _ANNOT = ("TICK", "REPEAT", "DETECTOR", "OBSERVABLE_INCLUDE", "SHIFT_COORDS", "QUBIT_COORDS")
-_PAIRED = ("CX", "CZ", "DEPOLARIZE2")
+_PAIRED = ("CX", "CZ", "DEPOLARIZE2", "PAULI_CHANNEL_2")
 SUPPORTED = tuple(sorted(set(_RESETS + _MEASURES + _GATES + _NOISE + _ANNOT + tuple(_ALIAS))))
 
 _LINE_RE = re.compile(r"^([A-Za-z_][A-Za-z0-9_]*)\s*(?:\(([^)]*)\))?\s*(.*)$")
@@ -67,10 +72,13 @@ def bern_threshold(p) -> np.ndarray:
 @dataclass(frozen=True)
 class Instruction:
     """One unrolled instruction: canonical name, probability argument (0 when
-    absent), targets (qubit, or qubit | INVERT for an inverted measurement)."""
+    absent), targets (qubit, or qubit | INVERT for an inverted measurement).
+    PAULI_CHANNEL_1 / 2: `args` holds the 3 / 15 probabilities and `p` their sum
+    (c_k = c_{k-1} + a_k in double, left to right)."""
     name: str
     p: float
     targets: Tuple[int, ...]
+    args: Tuple[float, ...] = ()
 
 
 @dataclass
@@ -158,8 +166,21 @@ def parse(text) -> ParsedCircuit:
                     raise ValueError(f"OBSERVABLE_INCLUDE needs an index: {line!r}") from None
                 out.observables.setdefault(i, []).extend(records(rest, line))
             elif name in _RESETS or name in _MEASURES or name in _GATES or name in _NOISE:
-                p = 0.0
-                if arg is not None:
+                p, chan = 0.0, ()
+                if name in CHANNEL_ARGS:
+                    try:
+                        chan = tuple(float(a) for a in arg.split(",")) if arg is not None and arg.strip() else ()
+                    except ValueError:
+                        raise ValueError(f"bad probability in line {line!r}") from None
+                    if len(chan) != CHANNEL_ARGS[name]:
+                        raise ValueError(f"{name} takes {CHANNEL_ARGS[name]} probabilities, not {len(chan)}: {line!r}")
+                    if not all(0.0 <= a <= 1.0 for a in chan):
+                        raise ValueError(f"probability outside [0, 1] in line {line!r}")
+                    for a in chan:
+                        p += a
+                    if p > 1.0 + 1e-12:
+                        raise ValueError(f"the probabilities of {name} sum to more than 1 in line {line!r}")
+                elif arg is not None:
                     if name in _RESETS or name in _GATES:
                         raise ValueError(f"{name} takes no argument: {line!r}")
                     try:
@@ -187,7 +208,7 @@ def parse(text) -> ParsedCircuit:
                     raise ValueError(f"odd number of targets for the two-qubit instruction {name}: {line!r}")
                 if name in _MEASURES:
                     out.num_measurements += len(tg)
-                out.instructions.append(Instruction(name, p, tuple(tg)))
+                out.instructions.append(Instruction(name, p, tuple(tg), chan))
             else:
                 raise _unsupported(name, line)
 
@@ -235,28 +256,29 @@ def compile_circuit(text, reference_sample=None, groups: Optional[Dict[str, obje
         ref = np.asarray(reference_sample).astype(bool).ravel()
         if ref.size != M:
             raise ValueError(f"reference_sample has {ref.size} bits, the circuit {M} measurements")
-    ops, targets, probs = [], [], []
+    ops, targets, probs, args = [], [], [], []
 
-    def emit(op, tg, p=0.0):
-        ops.append((op, len(targets), len(tg), 0))
+    def emit(op, tg, p=0.0, chan=()):
+        ops.append((op, len(targets), len(tg), len(args) if chan else 0))
         targets.extend(tg)
         probs.append(p)
+        args.extend(chan)
 
     emit(OP_R, list(range(Q)))  # Stim's initial state: every qubit reset
     rec = 0
     # adjacent instructions of one name and argument are one target list (the
     # reference writes a CX per line): the groups below then span the lines
-    fused: List[Tuple[str, float, list]] = []
+    fused: List[Tuple[str, float, list, tuple]] = []
     for ins in pc.instructions:
         if fused and ins.name not in _NOISE and fused[-1][0] == ins.name and fused[-1][1] == ins.p:
             fused[-1][2].extend(ins.targets)
         else:
-            fused.append((ins.name, ins.p, list(ins.targets)))
-    for name, p_arg, tg in fused:
+            fused.append((ins.name, ins.p, list(ins.targets), ins.args))
+    for name, p_arg, tg, chan in fused:
         if not tg:
             continue
         if name in _NOISE:
-            emit(OPCODES[name], tg, p_arg)
+            emit(OPCODES[name], tg, p_arg, chan)
             continue
         for g in _disjoint_groups(tg, 2 if name in _PAIRED else 1):
             if name in _MEASURES:
@@ -274,7 +296,8 @@ def compile_circuit(text, reference_sample=None, groups: Optional[Dict[str, obje
         ops=np.asarray(ops, dtype=np.int32).reshape(-1, 4), targets=np.asarray(targets, dtype=np.int32),
         probs=np.asarray(probs, dtype=np.float64),
         detectors=_rows_csr(pc.detectors, M),
-        observables=_rows_csr([pc.observables.get(i, []) for i in range(nobs)], M))
+        observables=_rows_csr([pc.observables.get(i, []) for i in range(nobs)], M),
+        args=np.asarray(args, dtype=np.float64))
     cc.thresholds = bern_threshold(cc.probs)
     if groups is None:
         groups = {"detectors": cc.detectors, "observables": cc.observables, "records": cc.record_rows()}
@@ -286,13 +309,14 @@ class CompiledCircuit:
     """A circuit as the device sampler takes it (see the module docstring)."""
     num_qubits: int
     num_measurements: int
-    ops: np.ndarray            # int32 [n_ops, 4]: opcode, first target, target count, 0
+    ops: np.ndarray            # int32 [n_ops, 4]: opcode, first target, target count, first argument (else 0)
     targets: np.ndarray        # int32 [n_targets]
     probs: np.ndarray          # float64 [n_ops]
     detectors: sp.csr_matrix   # [D, M] over absolute record indices
     observables: sp.csr_matrix  # [K, M]
     thresholds: np.ndarray = None   # uint32 [n_ops]: bern_threshold(probs)
     groups: Dict[str, sp.csr_matrix] = field(default_factory=dict)
+    args: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float64))   # float64: PAULI_CHANNEL arguments
     _handles: dict = field(default_factory=dict, repr=False)
 
     # ---- output groups
@@ -320,7 +344,7 @@ class CompiledCircuit:
             mat.sort_indices()
             g[name] = mat
         return CompiledCircuit(self.num_qubits, self.num_measurements, self.ops, self.targets, self.probs,
-                               self.detectors, self.observables, self.thresholds, g)
+                               self.detectors, self.observables, self.thresholds, g, self.args)
 
     @property
     def lds_bytes(self) -> int:
@@ -341,7 +365,7 @@ class CompiledCircuit:
 
     # ---- handles
     def _create(self, device: Optional[int], frame: Optional[str] = "auto"):
-        return create_handle(self.num_qubits, *self.abi_arrays(), device=device, frame=frame)
+        return create_handle(self.num_qubits, *self.abi_arrays(), device=device, frame=frame, args=self.args)
 
     def validate(self, frame: Optional[str] = "auto") -> dict:
         """Run the library's validation without a device
@@ -471,10 +495,13 @@ class CompiledCircuit:
 
 # ---- the raw ABI (tests hand qd_circuit_create_host broken programs through these)
 def create_handle(num_qubits, ops, targets, probs, group_rows, row_ptr, rec_idx, device: Optional[int] = None,
-                  frame=None):
+                  frame=None, args=None):
     """qd_circuit_create (device ordinal) or qd_circuit_create_host (None);
     with `frame` ("lds", "hbm", "auto", or a raw placement number) the _placed
-    entry points.  Raises _abi.QdecError carrying the library's code."""
+    entry points.  `args`: the PAULI_CHANNEL arguments; a program with such an
+    instruction goes through qd_circuit_create_args / _create_host_args (frame
+    None there means "lds", as in the entry points without a placement).  Raises
+    _abi.QdecError carrying the library's code."""
     from . import _abi
     lib = _abi.load()
     ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 4)
@@ -487,10 +514,21 @@ def create_handle(num_qubits, ops, targets, probs, group_rows, row_ptr, rec_idx,
             (row_ptr.size and rec_idx.size < max(int(row_ptr[-1]), 0)):
         raise ValueError("circuit arrays do not fit together")
     h = C.c_void_p()
-    args = (int(num_qubits), ops.shape[0], _abi.ptr(ops), targets.size, _abi.ptr(targets), _abi.ptr(probs),
-            group_rows.size, _abi.ptr(group_rows), _abi.ptr(row_ptr), _abi.ptr(rec_idx), C.byref(h))
-    if frame is not None:
-        place = FRAME_PLACEMENTS[frame] if isinstance(frame, str) else int(frame)
+    head = (int(num_qubits), ops.shape[0], _abi.ptr(ops), targets.size, _abi.ptr(targets), _abi.ptr(probs),
+            group_rows.size, _abi.ptr(group_rows), _abi.ptr(row_ptr), _abi.ptr(rec_idx))
+    place = None if frame is None else FRAME_PLACEMENTS[frame] if isinstance(frame, str) else int(frame)
+    if args is not None and ops.size and bool((ops[:, 0] >= OP_PC1).any()):
+        chan = np.ascontiguousarray(args, dtype=np.float64)
+        place = FRAME_PLACEMENTS["lds"] if place is None else place
+        if device is None:
+            _abi.check(lib.qd_circuit_create_host_args(place, *head, chan.size, _abi.ptr(chan), C.byref(h)),
+                       "qd_circuit_create_host_args")
+        else:
+            _abi.check(lib.qd_circuit_create_args(place, int(device), *head, chan.size, _abi.ptr(chan), C.byref(h)),
+                       "qd_circuit_create_args")
+        return h
+    args = head + (C.byref(h),)
+    if place is not None:
         if device is None:
             _abi.check(lib.qd_circuit_create_host_placed(place, *args), "qd_circuit_create_host_placed")
         else:

@@ -1335,7 +1335,7 @@ namespace {
 int create_circuit(int32_t placement, bool host_only, int32_t device, int32_t num_qubits, int32_t n_ops,
                    const int32_t* ops, int32_t n_targets, const int32_t* targets, const double* probs,
                    int32_t n_groups, const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
-                   qd_circuit** out) {
+                   qd_circuit** out, int32_t n_args = -1, const double* args = nullptr) {
     return guarded([&] {
         if (!out) throw Fail(-71, "circuit: null output handle");
         *out = nullptr;
@@ -1343,7 +1343,7 @@ int create_circuit(int32_t placement, bool host_only, int32_t device, int32_t nu
             throw Fail(-96, "circuit: unknown frame placement (0 LDS, 1 HBM, 2 auto)");
         std::unique_ptr<qd_circuit> C(new qd_circuit());
         build_circuit(C->hc, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows, row_ptr,
-                      rec_idx, placement != FP_LDS);
+                      rec_idx, placement != FP_LDS, n_args, args);
         C->placement = placement == FP_AUTO ? (C->hc.lds_bytes > kFrameLdsLimit ? FP_HBM : FP_LDS) : placement;
         C->host_only = host_only;
         const HostCircuit& h = C->hc;
@@ -1361,6 +1361,7 @@ int create_circuit(int32_t placement, bool host_only, int32_t device, int32_t nu
             C->num_cus = prop.multiProcessorCount;
             d.ops = static_cast<const FrameOpRec*>(C->arena.put(h.ops.data(), h.ops.size() * sizeof(FrameOpRec)));
             d.targets = static_cast<const int32_t*>(C->arena.put(h.targets.data(), h.targets.size() * 4));
+            d.cum = static_cast<const uint32_t*>(C->arena.put(h.cum.data(), h.cum.size() * 4));
             d.row_ptr = static_cast<const int32_t*>(C->arena.put(h.row_ptr.data(), h.row_ptr.size() * 4));
             d.rec_idx = static_cast<const int32_t*>(C->arena.put(h.rec_idx.data(), h.rec_idx.size() * 4));
         }
@@ -1473,6 +1474,24 @@ int qd_circuit_create_host_placed(int32_t placement, int32_t num_qubits, int32_t
                                   qd_circuit** out) {
     return create_circuit(placement, true, 0, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
                           group_rows, row_ptr, rec_idx, out);
+}
+
+int qd_circuit_create_args(int32_t placement, int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
+                           int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
+                           const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx, int32_t n_args,
+                           const double* args, qd_circuit** out) {
+    if (n_args < 0) return guarded([] { throw Fail(-71, "circuit: negative argument count"); });
+    return create_circuit(placement, false, device, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
+                          group_rows, row_ptr, rec_idx, out, n_args, args);
+}
+
+int qd_circuit_create_host_args(int32_t placement, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
+                                int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
+                                const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
+                                int32_t n_args, const double* args, qd_circuit** out) {
+    if (n_args < 0) return guarded([] { throw Fail(-71, "circuit: negative argument count"); });
+    return create_circuit(placement, true, 0, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
+                          group_rows, row_ptr, rec_idx, out, n_args, args);
 }
 
 int qd_circuit_set_frame_slots(qd_circuit* C, int64_t slots) {

@@ -11,13 +11,16 @@ namespace qdec {
 
 void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
                    const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
-                   const int32_t* row_ptr, const int32_t* rec_idx, bool beyond_lds) {
+                   const int32_t* row_ptr, const int32_t* rec_idx, bool beyond_lds, int32_t n_args,
+                   const double* args) {
     if (num_qubits < 1 || num_qubits > kFrameQubitMask || n_ops < 0 || n_targets < 0 || n_groups < 0 ||
         n_groups > kFrameGroups)
         throw Fail(-71, "circuit: bad sizes (1 <= qubits, 0 <= ops, targets, 0 <= groups <= 4)");
     if ((n_ops && (!ops || !probs)) || (n_targets && !targets) || (n_groups && (!group_rows || !row_ptr)))
         throw Fail(-71, "circuit: null program array");
+    if (n_args > 0 && !args) throw Fail(-71, "circuit: null program array");
     c.Q = num_qubits;
+    c.cum.clear();
     c.ops.clear();
     c.ops.reserve(n_ops);
     c.targets.assign(targets, targets + n_targets);
@@ -26,15 +29,18 @@ void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int3
     for (int32_t i = 0; i < n_ops; ++i) {
         const int32_t op = ops[4 * i], off = ops[4 * i + 1], cnt = ops[4 * i + 2];
         const std::string at = " (instruction " + std::to_string(i) + ")";
-        if (op < 0 || op >= FO_COUNT) throw Fail(-71, "circuit: unknown opcode" + at);
+        if (op < 0 || op >= FO_COUNT || (channel_args(op) && n_args < 0))
+            throw Fail(-71, "circuit: unknown opcode" + at);
         if (off < 0 || cnt < 0 || (int64_t)off + cnt > n_targets) throw Fail(-71, "circuit: target range outside the target array" + at);
-        const bool pair = op == FO_CX || op == FO_CZ || op == FO_DEP2;
+        const bool pair = op == FO_CX || op == FO_CZ || pair_noise(op);
         if (pair && (cnt & 1)) throw Fail(-71, "circuit: odd target count of a two-qubit instruction" + at);
         const bool meas = op == FO_M || op == FO_MX;
         const bool noise = op >= FO_XERR;
         const double p = probs[i];
         bool dup = false;
-        if (noise || meas) {
+        if (channel_args(op)) {
+            // checked against the sum of its arguments below (which rounding may leave a hair above 1)
+        } else if (noise || meas) {
             if (!(p >= 0.0 && p <= 1.0)) throw Fail(-75, "circuit: probability outside [0, 1]" + at);
         } else if (p != 0.0) {
             throw Fail(-75, "circuit: a gate or reset takes no probability" + at);
@@ -54,12 +60,31 @@ void build_circuit(HostCircuit& c, int32_t num_qubits, int32_t n_ops, const int3
         r.dup = dup;
         r.op = op, r.tgt_off = off, r.tgt_cnt = cnt;
         r.thr = bern_threshold(p);
+        const int32_t K = channel_args(op), a0 = ops[4 * i + 3];
+        if (!K) {
+            if (a0 != 0) throw Fail(-71, "circuit: an argument offset on an instruction without arguments" + at);
+        } else {
+            if (a0 < 0 || (int64_t)a0 + K > n_args) throw Fail(-71, "circuit: argument range outside the argument array" + at);
+            double sum = 0.0;  // c_k, summed left to right
+            r.cum_off = (int32_t)c.cum.size();
+            for (int32_t k = 0; k < K; ++k) {
+                const double a = args[a0 + k];
+                if (!(a >= 0.0 && a <= 1.0)) throw Fail(-75, "circuit: channel argument outside [0, 1]" + at);
+                sum += a;
+                c.cum.push_back(bern_threshold(sum));
+            }
+            if (sum > 1.0 + 1e-12) throw Fail(-75, "circuit: channel arguments sum to more than 1" + at);
+            if (!(p >= sum - 1e-12 && p <= sum + 1e-12))
+                throw Fail(-75, "circuit: the probability of a channel is not the sum of its arguments" + at);
+            r.thr = c.cum.back();
+        }
         r.site0 = (uint32_t)site, r.rsite0 = (uint32_t)rsite, r.rec0 = (int32_t)rec, r.fault0 = (int32_t)fault;
         fault += (uint64_t)fault_count(op, cnt, 0);
-        if (noise || meas) site += ((uint64_t)(op == FO_DEP2 ? cnt / 2 : cnt) + 3) / 4 * 4;
+        if (noise || meas) site += ((uint64_t)(pair_noise(op) ? cnt / 2 : cnt) + 3) / 4 * 4;
         if (meas || op == FO_R || op == FO_RX) rsite += (uint64_t)cnt;
         if (meas) rec += (uint64_t)cnt;
-        if (site >= (1ull << 31) || rsite >= (1ull << 31) || rec >= (1ull << 28) || fault >= (1ull << 30))
+        if (site >= (1ull << 31) || rsite >= (1ull << 31) || rec >= (1ull << 28) || fault >= (1ull << 30) ||
+            c.cum.size() >= (1ull << 30))
             throw Fail(-71, "circuit: too many draw sites, records or faults");
         c.ops.push_back(r);
     }

@@ -3,7 +3,8 @@
 // (qd_circuit_faults_device; frame_fault_kernel below).
 //
 // Stim's frame simulation of the gate set the storage experiment uses (H, CX, CZ,
-// resets and measurements in Z and X, X/Y/Z_ERROR, DEPOLARIZE1/2), bit-sliced:
+// resets and measurements in Z and X, X/Y/Z_ERROR, DEPOLARIZE1/2, PAULI_CHANNEL_1/2),
+// bit-sliced:
 // one wave runs 64 consecutive shots, and x[Q], z[Q] (the frame) and rec[M] (the
 // measurement record) are 64-bit words whose bit s is shot s of the wave.
 // The record is the flip against the noiseless reference sample; a measurement
@@ -40,7 +41,9 @@
 //     Philox4x32-10 block with counter (s / 4, 0, g_lo, g_hi); fires when u < T.
 //     DEPOLARIZE1: Pauli 1 + floor(3 u / T) (1 = X, 2 = Y, 3 = Z); DEPOLARIZE2:
 //     code 1 + floor(15 u / T), first qubit's Pauli = code >> 2, second's =
-//     code & 3 (0 = I).  Every instruction's first site is a multiple of 4.
+//     code & 3 (0 = I).  PAULI_CHANNEL_1 / 2, cumulative thresholds C_0 <= .. <=
+//     C_{K-1} = T (K = 3 / 15): Pauli / code 1 + #{j : C_j <= u}, so an outcome of
+//     probability 0 is never drawn.  Every instruction's first site is a multiple of 4.
 //   Randomisation site r of shot g: bit g % 32 of lane (g / 32) % 4 of the block
 //     with counter (r, 1, (g / 128)_lo, (g / 128)_hi).
 // so a shot's bits depend on (seed, stream_id, site, global shot) only.
@@ -190,19 +193,40 @@ __device__ __forceinline__ void frame_pairs(uint64_t* x, uint64_t* z, const int3
 }
 
 // What a noise site draws: a Bernoulli bit for a record (noisy M / MX) or for the
-// Pauli of X/Y/Z_ERROR, or the Pauli(s) of DEPOLARIZE1 / 2.
-enum SiteKind { SK_REC, SK_PAULI, SK_DEP1, SK_DEP2 };
+// Pauli of X/Y/Z_ERROR, or the Pauli(s) of DEPOLARIZE1 / 2 (equal shares of the
+// threshold) or of PAULI_CHANNEL_1 / 2 (cumulative thresholds).
+enum SiteKind { SK_REC, SK_PAULI, SK_DEP1, SK_DEP2, SK_PC1, SK_PC2 };
+constexpr bool site_pair(int kind) { return kind == SK_DEP2 || kind == SK_PC2; }
+
+// thresholds of a channel instruction a lane compares against: all but the last,
+// which is the instruction's thr (a fired lane has u below it)
+constexpr int site_thresholds(int kind) { return kind == SK_PC1 ? 2 : kind == SK_PC2 ? 14 : 0; }
+
+// 1 + the number of j < N with C[j] <= u: a compare and an add per entry
+template <int N>
+__device__ __forceinline__ uint32_t cumulative_index(uint32_t u, const uint32_t* C) {
+    uint32_t k = 1u;
+#pragma unroll
+    for (int j = 0; j < N; ++j) k += C[j] <= u ? 1u : 0u;
+    return k;
+}
 
 // The ballot words of one site from its u32, given f = the ballot of `fired`
-// (not 0): w = x, z of the (first) target and, DEPOLARIZE2, x, z of the second.
+// (not 0): w = x, z of the (first) target and, on a pair, x, z of the second.
+// C: the instruction's cumulative thresholds but the last (PAULI_CHANNEL_1 / 2 only).
 template <int KIND>
-__device__ __forceinline__ void site_words(int op, uint32_t u, uint32_t thr, bool fired, uint64_t f, uint64_t (&w)[4]) {
+__device__ __forceinline__ void site_words(int op, uint32_t u, uint32_t thr, const uint32_t* C, bool fired,
+                                           uint64_t f, uint64_t (&w)[4]) {
     w[2] = w[3] = 0ull;
-    if constexpr (KIND == SK_DEP1 || KIND == SK_DEP2) {
-        const uint32_t code = fired ? 1u + scaled_index(u, thr, KIND == SK_DEP1 ? 3u : 15u) : 0u;
-        const uint32_t Pa = KIND == SK_DEP1 ? code : code >> 2;
+    if constexpr (KIND != SK_REC && KIND != SK_PAULI) {
+        uint32_t code;
+        if constexpr (KIND == SK_PC1 || KIND == SK_PC2)
+            code = fired ? cumulative_index<site_thresholds(KIND)>(u, C) : 0u;
+        else
+            code = fired ? 1u + scaled_index(u, thr, KIND == SK_DEP1 ? 3u : 15u) : 0u;
+        const uint32_t Pa = site_pair(KIND) ? code >> 2 : code;
         w[0] = __ballot(pauli_x(Pa)), w[1] = __ballot(pauli_z(Pa));
-        if constexpr (KIND == SK_DEP2) w[2] = __ballot(pauli_x(code & 3u)), w[3] = __ballot(pauli_z(code & 3u));
+        if constexpr (site_pair(KIND)) w[2] = __ballot(pauli_x(code & 3u)), w[3] = __ballot(pauli_z(code & 3u));
     } else {
         w[0] = KIND == SK_REC || op != FO_ZERR ? f : 0ull;
         w[1] = KIND == SK_PAULI && op != FO_XERR ? f : 0ull;
@@ -233,16 +257,23 @@ __device__ __forceinline__ void apply_sites(bool dup, bool any, int lane, Apply&
 template <class Place, int KIND>
 __device__ __forceinline__ void frame_noise(const FrameOpRec& r, const int32_t* tg, int n, uint64_t* x, uint64_t* z,
                                             uint64_t* rec, int lane, uint32_t g_lo, uint32_t g_hi,
-                                            const SampleJob& j) {
+                                            const SampleJob& j, const uint32_t* cum = nullptr) {
     constexpr int kBatch = Place::kKeepSites ? 64 : 4;  // sites between two applications; 4 = one Philox block
+    // The channel's thresholds, the same in every lane, are loaded once, here: the loads are in flight during
+    // the first Philox block.  Loaded where a fired site needs them they cost a memory round trip per fired site
+    // (+ 13 % to + 23 % at p = 0.01).
+    constexpr int NC = site_thresholds(KIND);
+    uint32_t C[NC ? NC : 1] = {0u};
+#pragma unroll
+    for (int k = 0; k < NC; ++k) C[k] = cum[k];
     auto apply = [&](int site, const uint64_t(&w)[4]) {
         if constexpr (KIND == SK_REC) {
             rec[r.rec0 + site] ^= w[0];
         } else {
-            const int a = tg[KIND == SK_DEP2 ? 2 * site : site];
+            const int a = tg[site_pair(KIND) ? 2 * site : site];
             if (w[0]) x[a] ^= w[0];
             if (w[1]) z[a] ^= w[1];
-            if constexpr (KIND == SK_DEP2) {
+            if constexpr (site_pair(KIND)) {
                 const int b = tg[2 * site + 1];
                 if (w[2]) x[b] ^= w[2];
                 if (w[3]) z[b] ^= w[3];
@@ -263,7 +294,7 @@ __device__ __forceinline__ void frame_noise(const FrameOpRec& r, const int32_t* 
                 // with those the compiler threads the loop through a per-lane state variable, + 40 % time
                 if (f) {
                     uint64_t w[4];
-                    site_words<KIND>(r.op, u[l], r.thr, fired, f, w);
+                    site_words<KIND>(r.op, u[l], r.thr, C, fired, f, w);
                     if constexpr (Place::kKeepSites) {
                         if (lane == 4 * k + l) keep[0] = w[0], keep[1] = w[1], keep[2] = w[2], keep[3] = w[3];
                     } else if (lane == 0) {
@@ -387,6 +418,13 @@ __global__ __launch_bounds__(64) void frame_sample_kernel(DevCircuit c, Place pl
                 case FO_DEP2:
                     if (r.thr) frame_noise<Place, SK_DEP2>(r, tg, T / 2, x, z, rec, lane, g_lo, g_hi, j);
                     break;
+                case FO_PC1:
+                    if (r.thr) frame_noise<Place, SK_PC1>(r, tg, T, x, z, rec, lane, g_lo, g_hi, j, c.cum + r.cum_off);
+                    break;
+                case FO_PC2:
+                    if (r.thr)
+                        frame_noise<Place, SK_PC2>(r, tg, T / 2, x, z, rec, lane, g_lo, g_hi, j, c.cum + r.cum_off);
+                    break;
                 default:
                     break;
             }
@@ -405,7 +443,7 @@ __global__ __launch_bounds__(64) void frame_sample_kernel(DevCircuit c, Place pl
 // a flip) and kicks nothing.  At instruction i the lanes whose fault belongs to i
 // XOR their own bit into the word the fault names, after the instruction's own
 // work (a record flip follows the measurement, a gauge fault the reset).  Two
-// lanes may name one word (X_ERROR 0 1 0, a qubit in two DEPOLARIZE2 pairs, two
+// lanes may name one word (X_ERROR 0 1 0, a qubit in two DEPOLARIZE2 / PAULI_CHANNEL_2 pairs, two
 // gauge faults never): Place::inject.  Before a wave's first fault the frame is
 // all zero and stays so, so the wave starts at that fault's instruction, found by
 // bisection over the instructions' first-fault indices (non-decreasing; the last

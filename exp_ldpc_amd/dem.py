@@ -56,7 +56,8 @@ import numpy as np
 import scipy.sparse as sp
 
 __all__ = ["DemInstruction", "DetectorErrorModel", "parse_dem", "DetectorSpacetimeCode", "storage_experiment_dem",
-           "sample_dem", "sample_dem_device", "depolarize1_component", "depolarize2_component", "fault_mechanisms",
+           "sample_dem", "sample_dem_device", "depolarize1_component", "depolarize2_component",
+           "pauli_channel_components", "fault_mechanisms",
            "dem_from_symptoms", "check_deterministic_symptoms", "detector_error_model"]
 
 
@@ -312,6 +313,53 @@ def depolarize2_component(p: float) -> float:
     return 0.5 - 0.5 * (1.0 - 16.0 * p / 15.0) ** 0.125
 
 
+def _commutation_signs(n: int) -> np.ndarray:
+    """chi[P, Q] = +1 / -1 where the n-qubit Paulis P and Q commute / anticommute;
+    a Pauli is its code, two bits per qubit (0 I, 1 X, 2 Y, 3 Z), first qubit high."""
+    one = np.ones((4, 4))
+    one[1:, 1:] = 2.0 * np.eye(3) - 1.0          # two single-qubit Paulis anticommute iff both differ from I and from each other
+    chi = one
+    for _ in range(n - 1):
+        chi = np.kron(chi, one)
+    return chi
+
+
+_CHI = {3: _commutation_signs(1), 15: _commutation_signs(2)}
+
+
+def pauli_channel_components(probs, approximate_disjoint_errors: bool = False, name: str = "the channel") -> np.ndarray:
+    """q[K] with: independent flips of the K = 3 (X, Y, Z) or 15 (codes 1 .. 15:
+    IX .. ZZ) Paulis, probability q_P each, compose to exactly the channel that
+    applies Pauli P with probability probs[P - 1] (and nothing otherwise).  With
+    lambda_Q = sum_P p_P chi(P, Q) over all 4^n Paulis (p_I = 1 - sum probs):
+    q_P = 1/2 - 1/2 exp(-(2 / 4^n) sum_{Q != I} chi(P, Q) ln lambda_Q).  On the
+    uniform channels this is depolarize1_component / depolarize2_component.
+    The decomposition exists when every lambda_Q > 0 and every q_P >= 0 (a q_P in
+    (-1e-15, 0) is rounding and becomes 0); otherwise ValueError naming `name`,
+    or with approximate_disjoint_errors (Stim's keyword) the arguments themselves
+    as independent probabilities."""
+    p = np.asarray(probs, dtype=np.float64).ravel()
+    if p.size not in _CHI:
+        raise ValueError(f"{name}: a Pauli channel has 3 or 15 probabilities, not {p.size}")
+    if not ((p >= 0.0).all() and (p <= 1.0).all() and p.sum() <= 1.0 + 1e-12):
+        raise ValueError(f"{name}: probabilities outside [0, 1] or of sum above 1")
+    chi = _CHI[p.size]
+    full = np.concatenate([[1.0 - p.sum()], p])
+    lam = chi[:, 1:].T @ full                    # lambda_Q for Q != I
+    q = None
+    if (lam > 0.0).all():
+        q = 0.5 - 0.5 * np.exp(-(2.0 / (p.size + 1)) * (chi[1:, 1:] @ np.log(lam)))
+        q = np.where((q < 0.0) & (q > -1e-15), 0.0, q)
+        if (q < 0.0).any():
+            q = None
+    if q is None:
+        if approximate_disjoint_errors:
+            return p.copy()
+        raise ValueError(f"{name} has no decomposition into independent Pauli flips; "
+                         f"approximate_disjoint_errors=True takes its arguments as independent probabilities")
+    return q
+
+
 # members of the mechanisms of one DEPOLARIZE1 target (faults X = 0, Z = 1) and of
 # one DEPOLARIZE2 pair (X_a, Z_a, X_b, Z_b = 0 .. 3), -1 padded; Pauli 1 X, 2 Y, 3 Z
 _PAULI = {0: [], 1: [0], 2: [0, 1], 3: [1]}
@@ -319,18 +367,30 @@ _DEP1 = np.array([(_PAULI[P] + [-1] * 4)[:4] for P in (1, 2, 3)], np.int64)
 _DEP2 = np.array([(_PAULI[c >> 2] + [2 + k for k in _PAULI[c & 3]] + [-1] * 4)[:4] for c in range(1, 16)], np.int64)
 
 
-def fault_mechanisms(cc) -> Tuple[np.ndarray, np.ndarray]:
+def fault_mechanisms(cc, approximate_disjoint_errors: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """The independent error mechanisms of a CompiledCircuit, in program order:
     (probabilities float64 [K], members int64 [K, 4]: the elementary noise faults
     (include/qdec.h numbering) a mechanism fires together, -1 padded).
     X/Y/Z_ERROR(p) and M(p): one mechanism of probability p per target;
     DEPOLARIZE1(p): X, Y = {X, Z}, Z per target, q1 each; DEPOLARIZE2(p): the 15
     non-identity pairs (first qubit's Pauli = code >> 2, second's = code & 3 for
-    code 1 .. 15), q2 each.  Instructions with p = 0 contribute nothing."""
-    from .circuit import OP_DEP1, OP_DEP2, OP_M, OP_MX, OP_XERR
+    code 1 .. 15), q2 each.  PAULI_CHANNEL_1 / 2: the members of DEPOLARIZE1 / 2
+    with pauli_channel_components of the instruction's arguments; a component of
+    probability 0 is no mechanism.  Instructions with p = 0 contribute nothing."""
+    from .circuit import OP_DEP1, OP_DEP2, OP_M, OP_MX, OP_PC1, OP_PC2, OP_XERR
     probs, members, f = [], [], 0
-    for (op, _, cnt, _), p in zip(np.asarray(cc.ops).reshape(-1, 4).tolist(), np.asarray(cc.probs).tolist()):
-        if op == OP_DEP1:
+    for i, ((op, _, cnt, a0), p) in enumerate(zip(np.asarray(cc.ops).reshape(-1, 4).tolist(),
+                                                   np.asarray(cc.probs).tolist())):
+        if op in (OP_PC1, OP_PC2):
+            nf, unit, pat = (2 * cnt, 2, _DEP1) if op == OP_PC1 else (2 * cnt, 4, _DEP2)
+            q = 0.0
+            if p > 0:
+                a = np.asarray(cc.args, np.float64)[a0:a0 + pat.shape[0]]
+                name = f"PAULI_CHANNEL_{1 if op == OP_PC1 else 2}({', '.join(repr(float(v)) for v in a)}) (instruction {i})"
+                q = pauli_channel_components(a, approximate_disjoint_errors, name)
+                pat = pat[q > 0]
+                q = q[q > 0]
+        elif op == OP_DEP1:
             nf, unit, pat = 2 * cnt, 2, _DEP1
             q = depolarize1_component(p) if p > 0 else 0.0
         elif op == OP_DEP2:
@@ -344,7 +404,7 @@ def fault_mechanisms(cc) -> Tuple[np.ndarray, np.ndarray]:
             base = f + unit * np.arange(nf // unit, dtype=np.int64)
             mem = np.where(pat[None] >= 0, base[:, None, None] + pat[None], -1).reshape(-1, 4)
             members.append(mem)
-            probs.append(np.full(mem.shape[0], q, np.float64))
+            probs.append(np.broadcast_to(q, (nf // unit, pat.shape[0])).reshape(-1).astype(np.float64))
         f += nf
     if not members:
         return np.zeros(0, np.float64), np.zeros((0, 4), np.int64)
@@ -369,7 +429,8 @@ def _bits_of(words: np.ndarray, nbits: int) -> np.ndarray:
 
 
 def dem_from_symptoms(cc, det_sym, obs_sym, num_detectors: int | None = None,
-                      num_observables: int | None = None, mechanisms=None) -> DetectorErrorModel:
+                      num_observables: int | None = None, mechanisms=None,
+                      approximate_disjoint_errors: bool = False) -> DetectorErrorModel:
     """The DEM of a CompiledCircuit from the symptoms of its elementary noise
     faults: row f of det_sym / obs_sym = the detectors / observables fault f
     flips, as 0/1 rows (uint8) or packed words (int64 / uint64; then the counts
@@ -379,7 +440,7 @@ def dem_from_symptoms(cc, det_sym, obs_sym, num_detectors: int | None = None,
     p <- p (1 - p') + p' (1 - p), folded in mechanism order; empty symptoms are
     dropped; columns come in order of first appearance; a column with
     observables and no detector is kept.  `mechanisms`: (probabilities, members)
-    in place of fault_mechanisms(cc)."""
+    in place of fault_mechanisms(cc, approximate_disjoint_errors)."""
     det_in = np.asarray(det_sym.cpu().numpy() if hasattr(det_sym, "cpu") else det_sym)
     obs_in = np.asarray(obs_sym.cpu().numpy() if hasattr(obs_sym, "cpu") else obs_sym)
     packed_d, packed_o = det_in.dtype in (np.int64, np.uint64), obs_in.dtype in (np.int64, np.uint64)
@@ -388,7 +449,7 @@ def dem_from_symptoms(cc, det_sym, obs_sym, num_detectors: int | None = None,
     wd, wo = _as_words(det_in), _as_words(obs_in)
     if wd.shape[0] != wo.shape[0] or wd.shape[1] != (D + 63) // 64 or wo.shape[1] != (K + 63) // 64:
         raise ValueError("symptom rows do not fit the detector / observable counts")
-    probs, members = fault_mechanisms(cc) if mechanisms is None else mechanisms
+    probs, members = fault_mechanisms(cc, approximate_disjoint_errors) if mechanisms is None else mechanisms
     probs, members = np.asarray(probs, np.float64), np.asarray(members, np.int64).reshape(-1, 4)
     if members.size and members.max() >= wd.shape[0]:
         raise ValueError(f"{wd.shape[0]} symptom rows for {int(members.max()) + 1} elementary faults")
@@ -448,7 +509,7 @@ FAULT_WINDOW_BYTES = 256 << 20
 
 
 def detector_error_model(circuit, device: int = 0, check_deterministic: bool = True, detectors=None,
-                         observables=None) -> DetectorErrorModel:
+                         observables=None, approximate_disjoint_errors: bool = False) -> DetectorErrorModel:
     """The detector error model of a circuit (text, ParsedCircuit or
     CompiledCircuit) of the storage gate set: the counterpart of Stim's
     ``circuit.detector_error_model()`` (reference _experiment.py:174).  Detectors
@@ -458,7 +519,10 @@ def detector_error_model(circuit, device: int = 0, check_deterministic: bool = T
     in windows of at most FAULT_WINDOW_BYTES of symptoms.
     check_deterministic: the gauge faults (every reset's and measurement's
     randomised component) are propagated too, and a detector or observable one of
-    them flips raises ValueError (check_deterministic_symptoms)."""
+    them flips raises ValueError (check_deterministic_symptoms).
+    approximate_disjoint_errors: a PAULI_CHANNEL_1 / 2 without an exact
+    decomposition into independent flips (pauli_channel_components) contributes
+    its arguments as independent probabilities instead of raising ValueError."""
     import torch
     from .circuit import CompiledCircuit, compile_circuit
     cc = circuit if isinstance(circuit, CompiledCircuit) else compile_circuit(circuit)
@@ -466,6 +530,7 @@ def detector_error_model(circuit, device: int = 0, check_deterministic: bool = T
                            "observables": cc.observables if observables is None else observables})
     D, K = prog.groups["detectors"].shape[0], prog.groups["observables"].shape[0]
     from .circuit import handle_fault_info
+    mechanisms = fault_mechanisms(prog, approximate_disjoint_errors)   # refuses a channel before any launch
     row_bytes = 8 * ((D + 63) // 64 + (K + 63) // 64)
     window = max(64, FAULT_WINDOW_BYTES // max(row_bytes, 1) // 64 * 64)   # whole 64-fault words
 
@@ -485,6 +550,6 @@ def detector_error_model(circuit, device: int = 0, check_deterministic: bool = T
             noise, gauge = handle_fault_info(prog.handle(device))
             if check_deterministic:
                 check_deterministic_symptoms(*symptoms(1, gauge), D, K)
-            return dem_from_symptoms(prog, *symptoms(0, noise), D, K)
+            return dem_from_symptoms(prog, *symptoms(0, noise), D, K, mechanisms=mechanisms)
     finally:
         prog.close()

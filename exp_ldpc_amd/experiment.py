@@ -276,7 +276,7 @@ class BatchPipeline:
     def __init__(self, code, rounds: int, mode: str, bp_osd_options: Dict, priors: Tuple[float, float], *,
                  device: int = 0, precision: str = "f64", use_x_logicals: bool = False, osd_threads: int = 0,
                  noise=None, dem_source: str | None = None, sim=None, osd_rows: str | None = None,
-                 llr_budget_bytes: int = DEFAULT_LLR_BUDGET):
+                 llr_budget_bytes: int = DEFAULT_LLR_BUDGET, approximate_disjoint_errors: bool = False):
         if mode not in DECODER_MODES:
             raise RuntimeError("Unknown decoder operation mode")
         if dem_source not in (None, "circuit"):
@@ -290,6 +290,8 @@ class BatchPipeline:
         if self.llr_budget_bytes <= 0:
             raise ValueError("llr_budget_bytes must be positive")
         self.dem_source = None
+        # dem.detector_error_model's: PAULI_CHANNELs without an exact decomposition
+        self.approximate_disjoint_errors = bool(approximate_disjoint_errors)
         if mode == "bpssf" and rounds > 0:
             mode = "bpssf_hybrid"
         self.mode = mode
@@ -393,7 +395,8 @@ class BatchPipeline:
         k = L.shape[0]
         on_records = sp.hstack([sp.csr_matrix((k, cc.num_measurements - n), dtype=L.dtype), L]).tocsr()
         self.dem_model = detector_error_model(cc, device=self.device, detectors=cc.detectors,
-                                              observables=on_records)
+                                              observables=on_records,
+                                              approximate_disjoint_errors=self.approximate_disjoint_errors)
         full = DetectorSpacetimeCode(self.dem_model)
         Hc = sp.csc_matrix(full.fault_check_matrix)
         seen = np.diff(Hc.indptr) > 0
@@ -708,12 +711,13 @@ def run_simulation(samples, code, meas_prior, data_prior, noise_model, noise_mod
                    decoder_mode, *, seed: int = DEFAULT_SEED, stream_id: int = 0, shot0: int = 0, device: int = 0,
                    batch: int = 1 << 18, precision: str = "f64", stats: dict | None = None,
                    dem_source: str | None = None, osd_rows: str | None = None,
-                   llr_budget_bytes: int = DEFAULT_LLR_BUDGET):
+                   llr_budget_bytes: int = DEFAULT_LLR_BUDGET, approximate_disjoint_errors: bool = False):
     """Sample and decode `samples` shots on one GPU; returns a bool ndarray of
     logical-failure flags (reference run_simulation, _experiment.py:154-210,
     which returns a list of the same flags).  dem_source="circuit": bpd_detector
     decodes the DEM extracted from the circuit under any noise model (the
-    default under every rewriter but depolarizing_noise)."""
+    default under every rewriter but depolarizing_noise);
+    approximate_disjoint_errors: dem.detector_error_model's, for that DEM."""
     torch = _torch()
     x_steps, z_steps = _steps(code.checks)
     sim = build_storage_simulation(rounds, noise_model(**noise_model_args), code, use_x_logicals=False)
@@ -721,7 +725,7 @@ def run_simulation(samples, code, meas_prior, data_prior, noise_model, noise_mod
     dp = data_prior(x_steps, z_steps)
     pipe = BatchPipeline(code, rounds, decoder_mode, bp_osd_options, (dp, mp), device=device, precision=precision,
                          noise=noise_model(**noise_model_args), dem_source=dem_source, sim=sim, osd_rows=osd_rows,
-                         llr_budget_bytes=llr_budget_bytes)
+                         llr_budget_bytes=llr_budget_bytes, approximate_disjoint_errors=approximate_disjoint_errors)
     out = np.zeros(samples, dtype=bool)
     agg = {"bp_converged": 0, "iters_sum": 0, "ssf_steps_sum": 0}
     with torch.cuda.device(device):
@@ -917,7 +921,8 @@ HBM_PEAK_BYTES_S = 8.0e12  # MI355X HBM3E peak (MI355X_MICROARCH.md)
 
 def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_prior, *, gpus: int | None = None,
             devices=None, seed: int = DEFAULT_SEED, batch: int = 1 << 18, precision: str = "f64",
-            checkpoint: str | None = None, dem_source: str | None = None, osd_rows: str | None = None, **kwargs):
+            checkpoint: str | None = None, dem_source: str | None = None, osd_rows: str | None = None,
+            approximate_disjoint_errors: bool = False, **kwargs):
     """Sweep the physical error rate (reference p_sweep, misc/p_sweep.py:17-40).
     Shots are sharded over `gpus` devices by index (shard d decodes a
     contiguous shot range); exactly `samples` shots per point.  `devices`
@@ -942,7 +947,8 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
 
     dem_source: BatchPipeline's; points decoded on the circuit's own DEM carry
     dem_sector = "circuit".  osd_rows: BatchPipeline's (where the OSD stage runs;
-    the failure counts do not depend on it)."""
+    the failure counts do not depend on it).  approximate_disjoint_errors:
+    dem.detector_error_model's, for the circuit's DEM."""
     import pandas as pd
     torch = _torch()
     done = _load_checkpoint(checkpoint)
@@ -958,7 +964,8 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
         nm_args = noise_model_args(p_ph)
         dp = data_prior(p_ph, x_steps, z_steps)
         mp = meas_prior(p_ph, x_steps, z_steps)
-        fp = _config_fingerprint(code, rounds, mode if dem_source is None else f"{mode}/dem={dem_source}",
+        fp = _config_fingerprint(code, rounds, (mode if dem_source is None else f"{mode}/dem={dem_source}") +
+                                 ("/approximate_disjoint_errors" if approximate_disjoint_errors else ""),
                                  bp_osd_options, precision, seed, samples, pi, noise=(noise_model, nm_args, dp, mp))
         prev = done.get((float(p_ph), fp))
         if prev is not None:
@@ -970,7 +977,8 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
 
         def pipeline(d):
             return BatchPipeline(code, rounds, mode, bp_osd_options, (dp, mp), device=d, precision=precision,
-                                 noise=nm, dem_source=dem_source, sim=sim, osd_rows=osd_rows)
+                                 noise=nm, dem_source=dem_source, sim=sim, osd_rows=osd_rows,
+                                 approximate_disjoint_errors=approximate_disjoint_errors)
         pipes = [pipeline(d) for d in devs]
         per = math.ceil(samples / ndev)
         shards = [(i, i * per, min(samples, (i + 1) * per)) for i in range(ndev)]
@@ -1076,14 +1084,18 @@ def p_sweep_main(noise_model_args, noise_model, meas_prior, data_prior):
                              "bposd_detector)")
     parser.add_argument("--checkpoint", type=str, default=None,
                         help="CSV that each finished point is appended to; finished points are skipped on restart")
+    parser.add_argument("--approximate_disjoint_errors", action="store_true",
+                        help="circuit DEM: a PAULI_CHANNEL without an exact decomposition into independent "
+                             "mechanisms contributes its arguments as independent probabilities (default: refused)")
     args = parser.parse_args(sys.argv[1:])
     code = load_code(args)
     bp_osd_options = unpack_bposd_args(args, code)
-    sweep = np.linspace(*args.p_sweep) if args.linspace else np.geomspace(*args.p_sweep)
+    sweep =np.linspace(*args.p_sweep) if args.linspace else np.geomspace(*args.p_sweep)
     result = p_sweep(samples=args.samples, code=code, rounds=args.rounds, noise_model=noise_model,
                      noise_model_args=noise_model_args, meas_prior=meas_prior, data_prior=data_prior,
                      p_values=sweep, decoder_mode=args.decoder_mode, bp_osd_options=bp_osd_options,
                      gpus=args.gpus, devices=args.devices, seed=args.seed, batch=args.batch, precision=args.precision,
-                     checkpoint=args.checkpoint, osd_rows=args.osd_rows)
+                     checkpoint=args.checkpoint, osd_rows=args.osd_rows,
+                     approximate_disjoint_errors=args.approximate_disjoint_errors)
     result.to_csv(sys.stdout)
     return result

@@ -2,7 +2,8 @@
 
 Mirrors ``python/qldpc/noise_model.py``: ``depolarizing_noise(p, pm)`` (:117-123),
 ``trivial_noise()`` (:10-12) and ``circuit_noise(p, pm)`` (:125-151) return
-rewriter objects whose ``rewrite(targets, circuit)`` inserts noise into a
+rewriter objects (``biased_circuit_noise(p, eta, pm)`` is this project's own:
+``circuit_noise`` with PAULI_CHANNEL_1 / PAULI_CHANNEL_2 of bias eta) whose ``rewrite(targets, circuit)`` inserts noise into a
 Stim-style circuit listing exactly where the reference does (the rewrite rules
 are pinned by the reference's golden tests, tests/test_storage_sim.py:13-77,
 restated in tests/test_noise_model.py).  The objects also carry their
@@ -19,7 +20,8 @@ import re
 from dataclasses import dataclass, field
 from typing import Callable, Iterable, List
 
-__all__ = ["NoiseRewriter", "depolarizing_noise", "trivial_noise", "circuit_noise", "circuit_ticks",
+__all__ = ["NoiseRewriter", "depolarizing_noise", "trivial_noise", "circuit_noise", "biased_circuit_noise",
+           "biased_channel_1", "biased_channel_2", "circuit_ticks",
            "tokenize_line", "get_two_qubit_targets"]
 
 _MEASUREMENT_GATES = ["M", "MZ", "MX", "MY", "MPP", "MR", "MRZ", "MRX", "MRY"]
@@ -123,3 +125,49 @@ def circuit_noise(p: float, pm: float | None = None) -> NoiseRewriter:
             out.append(f"DEPOLARIZE1({p}) " + " ".join(str(q) for q in sorted(ones)))
         return out
     return NoiseRewriter(rewrite, kind="circuit", p=float(p), pm=float(pm))
+
+
+def biased_channel_1(p: float, eta: float):
+    """(px, py, pz) of a single-qubit Pauli channel of strength p and bias eta =
+    pz / (px + py): pz = p eta / (1 + eta), px = py = p / (2 (1 + eta)).
+    eta = 1/2 is DEPOLARIZE1(p); eta -> infinity is Z_ERROR(p)."""
+    pxy = p / (2.0 * (1.0 + eta))
+    return (pxy, pxy, p * eta / (1.0 + eta))
+
+
+def biased_channel_2(p: float, eta: float):
+    """The 15 probabilities (IX, IY, IZ, XI, .. ZZ) of a two-qubit Pauli channel of
+    strength p whose Z-only Paulis IZ, ZI, ZZ are favoured with eta2 = eta / 2:
+    p eta2 / (3 (1 + eta2)) each, the other twelve p / (12 (1 + eta2)) each.
+    eta = 1/2 is DEPOLARIZE2(p)."""
+    eta2 = eta / 2.0
+    z_only, other = p * eta2 / (3.0 * (1.0 + eta2)), p / (12.0 * (1.0 + eta2))
+    return tuple(z_only if code in (3, 12, 15) else other for code in range(1, 16))
+
+
+def biased_circuit_noise(p: float, eta: float, pm: float | None = None) -> NoiseRewriter:
+    """circuit_noise with dephasing-biased channels: PAULI_CHANNEL_2(biased_channel_2
+    (p, eta)) on every gate pair and PAULI_CHANNEL_1(biased_channel_1(p, eta)) on
+    every idle qubit of every tick, measurements flipped with probability pm
+    (default p).  eta = 1/2 is circuit_noise(p, pm); as eta grows both channels
+    tend to pure dephasing.  For p <= 0.1 and eta in 0.5 .. 10^4 both have an
+    exact decomposition into independent mechanisms (dem.pauli_channel_components)."""
+    if not eta > 0:
+        raise ValueError("the bias eta must be positive")
+    if pm is None:
+        pm = p
+    one = ", ".join(repr(float(a)) for a in biased_channel_1(p, eta))
+    two = ", ".join(repr(float(a)) for a in biased_channel_2(p, eta))
+
+    def rewrite(targets, circuit):
+        support = set(targets.data) | set(targets.ancillas)
+        out = []
+        for step in circuit_ticks(circuit):
+            pairs = [pq for l in step for pq in get_two_qubit_targets(l)]
+            ones = support - {q for pq in pairs for q in pq}
+            out.extend(_noisy_measurement(l, pm) for l in step)
+            if pairs:
+                out.append(f"PAULI_CHANNEL_2({two}) " + " ".join(f"{a} {b}" for a, b in pairs))
+            out.append(f"PAULI_CHANNEL_1({one}) " + " ".join(str(q) for q in sorted(ones)))
+        return out
+    return NoiseRewriter(rewrite, kind="biased_circuit", p=float(p), pm=float(pm), params={"eta": float(eta)})

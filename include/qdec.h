@@ -190,15 +190,24 @@ int qd_graph_sample_tables_copy(const qd_graph* g, uint32_t* thr, int32_t* crow)
  * 193-197) for circuits of the storage experiment's gate set under any noise
  * rewriter (noise_model.py:117-151).  A circuit is not a graph and has a handle
  * of its own.  The program (built by exp_ldpc_amd/circuit.py):
- *   ops      int32 [n_ops][4]: opcode, first target, target count, 0.  Opcodes:
+ *   ops      int32 [n_ops][4]: opcode, first target, target count, first
+ *            argument (0 unless the opcode takes arguments).  Opcodes:
  *            0 H, 1 CX, 2 CZ, 3 R, 4 RX, 5 M, 6 MX, 7 X_ERROR, 8 Y_ERROR,
- *            9 Z_ERROR, 10 DEPOLARIZE1, 11 DEPOLARIZE2 (CX, CZ, DEPOLARIZE2:
- *            targets in pairs).  MR / MRX are an M / MX followed by an R / RX.
+ *            9 Z_ERROR, 10 DEPOLARIZE1, 11 DEPOLARIZE2, 12 PAULI_CHANNEL_1,
+ *            13 PAULI_CHANNEL_2 (CX, CZ, DEPOLARIZE2, PAULI_CHANNEL_2: targets in
+ *            pairs).  MR / MRX are an M / MX followed by an R / RX.
  *   targets  int32 [n_targets]: qubit indices; a measurement target with bit 30
  *            set has its record inverted (a reference sample of 1)
  *   probs    double [n_ops]: the probability of a noise instruction, the record
  *            flip probability of a measurement, 0 otherwise; converted to u32
  *            thresholds as in qd_sample_faults_device
+ *   args     double [n_args] (qd_circuit_create_args / _create_host_args only):
+ *            PAULI_CHANNEL_1 reads 3 entries from its first argument on, the
+ *            probabilities of X, Y, Z; PAULI_CHANNEL_2 reads 15, those of the
+ *            two-qubit codes 1 .. 15 (Stim's order IX, IY, IZ, XI, .. ZZ: first
+ *            qubit's Pauli = code >> 2, second's = code & 3; 0 I, 1 X, 2 Y, 3 Z).
+ *            Its entry of probs is their sum c_{K-1}, with c_k = c_{k-1} + a_k
+ *            in double, left to right
  *   groups   up to 4 output groups; group g has group_rows[g] rows, each the
  *            parity of a set of measurement records: one CSR over absolute
  *            record indices, the groups' rows concatenated (row_ptr[rows + 1],
@@ -213,6 +222,12 @@ int qd_graph_sample_tables_copy(const qd_graph* g, uint32_t* thr, int32_t* crow)
  * parallel group, -75 probability outside [0, 1], -76 the circuit needs more
  * than 160 KiB of LDS (16 B per qubit + 8 B per measurement), -15 device
  * ordinal.  qd_circuit_create_host validates only and makes no HIP call.
+ * qd_circuit_create_args / qd_circuit_create_host_args are qd_circuit_create_placed
+ * / _create_host_placed with the argument array in front of `out`; only they take
+ * opcodes 12 and 13 (the four others refuse them as unknown, -71).  Further
+ * refusals: -71 n_args < 0, an instruction's arguments outside the array, or a
+ * non-zero first argument on any other opcode; -75 an argument outside [0, 1], a
+ * sum above 1 + 1e-12, or an entry of probs further than 1e-12 from the sum.
  * qd_circuit_info: out[10] = qubits, measurements, rows of groups 0..3, LDS
  * bytes (16 Q + 8 M under every placement), instructions, Bernoulli / Pauli draw
  * sites, randomisation sites.
@@ -261,6 +276,14 @@ int qd_circuit_create_host_placed(int32_t placement, int32_t num_qubits, int32_t
                                   int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
                                   const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
                                   qd_circuit** out);
+int qd_circuit_create_args(int32_t placement, int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
+                           int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
+                           const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx, int32_t n_args,
+                           const double* args, qd_circuit** out);
+int qd_circuit_create_host_args(int32_t placement, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
+                                int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
+                                const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
+                                int32_t n_args, const double* args, qd_circuit** out);
 int qd_circuit_set_frame_slots(qd_circuit* c, int64_t slots);
 int qd_circuit_frame_info(const qd_circuit* c, int64_t out[4]);
 int qd_circuit_op_flags_copy(const qd_circuit* c, int32_t* dup);
@@ -281,8 +304,12 @@ int qd_circuit_info(const qd_circuit* c, int64_t out[10]);
  *     (s / 4, 0, g_lo, g_hi); the site fires when u < T.  DEPOLARIZE1 applies
  *     Pauli 1 + floor(3 u / T) (1 X, 2 Y, 3 Z); DEPOLARIZE2 draws code 1 +
  *     floor(15 u / T) and applies Pauli code >> 2 to the pair's first qubit and
- *     code & 3 to its second (0 I).  Sites number the targets (pairs for
- *     DEPOLARIZE2) of the noise and measurement instructions in program order,
+ *     code & 3 to its second (0 I).  PAULI_CHANNEL_1 / 2 with arguments a_0 ..
+ *     a_{K-1} (K = 3 / 15): C_k = the u32 threshold of c_k; T = C_{K-1}; a fired
+ *     site applies Pauli (PAULI_CHANNEL_1) or code (PAULI_CHANNEL_2, as
+ *     DEPOLARIZE2) 1 + #{j < K : C_j <= u}, so an outcome whose argument is 0 never
+ *     occurs.  Sites number the targets (pairs for DEPOLARIZE2 and
+ *     PAULI_CHANNEL_2) of the noise and measurement instructions in program order,
  *     each instruction starting at the next multiple of 4.
  *   randomisation site r, shot g: bit g % 32 of lane (g / 32) % 4 of the block
  *     with counter (r, 1, (g / 128)_lo, (g / 128)_hi); sites number the targets
@@ -303,6 +330,7 @@ int qd_circuit_sample_device(qd_circuit* c, uint32_t seed, uint32_t stream_id, i
  *     X_ERROR / Y_ERROR / Z_ERROR: one per target, the named Pauli (Y: x and z);
  *     DEPOLARIZE1: two per target, fault 2e = X on target e, 2e + 1 = Z;
  *     DEPOLARIZE2: four per pair: X_a, Z_a, X_b, Z_b;
+ *     PAULI_CHANNEL_1 / PAULI_CHANNEL_2: as DEPOLARIZE1 / DEPOLARIZE2;
  *     M / MX: one per target, a flip of that record (MR(p) is an M(p) then an R).
  *   gauge faults (kind 1): one per randomisation site in the sampler's site order
  *     (the targets of R, RX, M, MX, the opening R included); the injected bit is

@@ -3,7 +3,8 @@
 // runtime and no GPU stack:
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-//       tools/circuit_check.cpp exp_ldpc_amd/csrc/qdec_circuit.cpp -o circuit_check
+//       tools/circuit_check.cpp exp_ldpc_amd/csrc/qdec_circuit.cpp exp_ldpc_amd/csrc/qdec_tables.cpp \
+//       -o circuit_check
 //   circuit_check   ->  one line per case, "<case> <code>", exit 0 when every code is the expected one
 //
 // A valid two-qubit program and one broken variant per refusal of
@@ -12,6 +13,9 @@
 // Every program that validates also has its elementary-fault tables built
 // (circuit_fault_table, both kinds) into arrays of exactly the counted size and
 // checked: instruction and target in range, the faults in program order.
+// The PAULI_CHANNEL_1 / 2 cases go through the argument array of
+// qd_circuit_create_args: offsets before, across and behind its end, arguments and
+// sums out of range, and the entry points without the array.
 #include <cstdio>
 #include <vector>
 
@@ -26,7 +30,24 @@ struct Program {
     std::vector<int32_t> targets{0, 1, 0, 0, 1};
     std::vector<double> probs{0.0, 0.5, 0.25};
     std::vector<int32_t> rows{1}, row_ptr{0, 2}, rec_idx{0, 1};
+    bool with_args = false;  // the entry points that take an argument array
+    std::vector<double> args;
 };
+
+// PAULI_CHANNEL_1 on three targets (one named twice), PAULI_CHANNEL_2 on two pairs, a measurement
+static Program channels() {
+    Program p;
+    p.Q = 3;
+    p.ops = {FO_PC1, 0, 3, 0, FO_PC2, 3, 4, 3, FO_M, 7, 3, 0};
+    p.targets = {0, 1, 0, 0, 1, 1, 2, 0, 1, 2};
+    p.args = {0.02, 0.05, 0.11};
+    double sum = 0.0;
+    for (int k = 1; k <= 15; ++k) p.args.push_back(0.004 * k), sum += 0.004 * k;
+    p.probs = {0.02 + 0.05 + 0.11, sum, 0.0};
+    p.rows = {1}, p.row_ptr = {0, 1}, p.rec_idx = {2};
+    p.with_args = true;
+    return p;
+}
 
 // 0 when the fault tables of a validated program are consistent with it
 static int walk_faults(const HostCircuit& c) {
@@ -48,7 +69,12 @@ static int code_of(const Program& p, int* faults = nullptr) {
     HostCircuit c;
     try {
         build_circuit(c, p.Q, (int32_t)p.ops.size() / 4, p.ops.data(), (int32_t)p.targets.size(), p.targets.data(),
-                      p.probs.data(), (int32_t)p.rows.size(), p.rows.data(), p.row_ptr.data(), p.rec_idx.data());
+                      p.probs.data(), (int32_t)p.rows.size(), p.rows.data(), p.row_ptr.data(), p.rec_idx.data(), false,
+                      p.with_args ? (int32_t)p.args.size() : -1, p.args.data());
+        for (const FrameOpRec& r : c.ops)  // the kernel reads channel_args(op) thresholds from cum_off on
+            if (r.cum_off < 0 || (size_t)r.cum_off + channel_args(r.op) > c.cum.size() ||
+                (channel_args(r.op) && c.cum[r.cum_off + channel_args(r.op) - 1] != r.thr))
+                return -1;
         if (faults) faults[0] = fault_total(c, 0), faults[1] = fault_total(c, 1);
         if (walk_faults(c) != 0) return -1;
         int32_t one = 0;
@@ -99,5 +125,39 @@ int main() {
     expect("csr_start", p, -71);
     p = Program(), p.Q = (int32_t)(kFrameLdsLimit / 16) + 1;
     expect("lds_limit", p, -76);
+    // PAULI_CHANNEL_1 / 2
+    p = channels();
+    expect("channels", p, 0);
+    code_of(p, faults);  // two faults per PAULI_CHANNEL_1 target, four per PAULI_CHANNEL_2 pair, three measurements
+    std::printf("channel_faults %d %d\n", faults[0], faults[1]);
+    bad += faults[0] != 6 + 8 + 3 || faults[1] != 3;
+    p = channels(), p.with_args = false;
+    expect("channels_without_array", p, -71);
+    p = channels(), p.ops[7] = 4;  // the last of its 15 arguments lies one past the end
+    expect("arg_range_across_end", p, -71);
+    p = channels(), p.ops[7] = 18;
+    expect("arg_range_behind_end", p, -71);
+    p = channels(), p.ops[3] = -1;
+    expect("arg_range_negative", p, -71);
+    p = channels(), p.ops[3] = 0x7fffffff;
+    expect("arg_range_overflow", p, -71);
+    p = channels(), p.args.clear();
+    expect("arg_array_empty", p, -71);
+    p = channels(), p.ops[11] = 1;
+    expect("arg_offset_on_measurement", p, -71);
+    p = Program(), p.with_args = true, p.ops[3] = 2;
+    expect("arg_offset_on_gate", p, -71);
+    p = channels(), p.args[1] = -0.05, p.probs[0] = 0.08;
+    expect("arg_negative", p, -75);
+    p = channels(), p.args[4] = 1.5;
+    expect("arg_above_one", p, -75);
+    p = channels(), p.args[2] = 0.9301, p.probs[0] = 1.0001;
+    expect("arg_sum_above_one", p, -75);
+    p = channels(), p.probs[1] += 1e-9;
+    expect("probability_is_not_the_sum", p, -75);
+    p = channels(), p.targets[4] = 3;
+    expect("channel_qubit_out_of_range", p, -72);
+    p = channels(), p.ops[6] = 3, p.ops[9] = 6, p.ops[10] = 4;
+    expect("channel_odd_pairs", p, -71);
     return bad ? 1 : 0;
 }
