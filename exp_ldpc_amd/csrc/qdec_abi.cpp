@@ -1,68 +1,12 @@
-// qdec_abi.cpp -- extern "C" entry points of libqdec_hip.so (include/qdec.h).
+// qdec_abi.cpp -- extern "C" entry points of libqdec_hip.so (include/qdec.h)
+// on graph handles; qdec_abi_circuit.cpp has those of compiled circuits.
 //
 // The graph handle: its tables come from the host builders (qdec_tables.cpp)
-// through a device sink; this file owns the streams, events, workspaces and
-// launches.  No C++ exception crosses the ABI.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/qdec.h"
-#include "qdec_internal.h"
-#include "qdec_tables.h"
+// through a device sink (qdec_abi.h); this file owns the streams, events,
+// workspaces and launches.  No C++ exception crosses the ABI.
+#include "qdec_abi.h"
 
 using namespace qdec;
-
-namespace {
-
-thread_local std::string g_last_error;
-
-void hip_check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw Fail(-100 - (int)e, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-template <typename F>
-int guarded(F&& f) {
-    try {
-        f();
-        return 0;
-    } catch (const Fail& e) {
-        g_last_error = e.what();
-        return e.code;
-    } catch (const std::exception& e) {
-        g_last_error = e.what();
-        return -99;
-    } catch (...) {
-        g_last_error = "unknown error";
-        return -99;
-    }
-}
-
-// The tables of a device graph: one allocation each, owned by the graph.  (A
-// host-only graph, qd_graph_create_host, keeps HostSink copies instead and
-// makes no HIP call.)
-struct DeviceSink : TableSink {
-    std::vector<void*> ptrs;
-    const void* put(const void* src, size_t bytes) override {
-        void* d = nullptr;
-        hip_check(hipMalloc(&d, std::max<size_t>(bytes, 16)), "hipMalloc");
-        ptrs.push_back(d);
-        if (bytes) hip_check(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice), "hipMemcpy H2D");
-        return d;
-    }
-    void release() override {
-        for (void* p : ptrs) (void)hipFree(p);
-        ptrs.clear();
-    }
-    ~DeviceSink() override { release(); }
-};
-
-}  // namespace
 
 // the builders' HostGraph (tables, host CSR / CSC copies, sinks) plus the
 // runtime state of the handle
@@ -72,25 +16,19 @@ struct qd_graph : HostGraph {
     hipStream_t stream = nullptr;
     bool has_priors = false;   // BP priors: every probability inside (0, 1)
     bool has_thr = false;      // qd_graph_set_priors succeeded: the fault sampler's thresholds exist
-    // workspace for the host-buffer API (grow only)
-    void* ws = nullptr;
-    size_t ws_bytes = 0;
-    // SSF work queue scratch (grow only): count | idx[B] | x[B][n] | r[B][m]
-    void* qws = nullptr;
-    int64_t q_cap = 0;
+    // workspace for the host-buffer API (bytes)
+    DevBuf ws;
+    // SSF work queue scratch (shots): count | idx[B] | x[B][n] | r[B][m]
+    DevBuf qws;
     // HBM message scratch for the workgroup kernels on graphs too large for LDS
-    void* mws = nullptr;
-    size_t mws_bytes = 0;
+    MessageScratch mws;
     // QD_INPUT_PACKED decodes off the two-pass path: the inputs expanded to
-    // byte rows (grow only; DecodeArgs::unpack_buf)
-    void* ubuf = nullptr;
-    size_t ubuf_bytes = 0;
+    // byte rows (bytes; DecodeArgs::unpack_buf)
+    DevBuf ubuf;
     // compact-list segment counters, two sets (DecodeArgs::cmp_count_next):
     // two-pass decodes alternate between them, each triage zeroing the other
     void* cmpc = nullptr;
     int cmp_par = 0;
-    size_t mws_failed = 0;  // smallest scratch size whose allocation failed (0: none)
-    uint64_t mws_capped_calls = 0;  // calls served the reduced scratch since the failure
     // kernel timing ring (qd_graph_set_timing): 3 events per decode call
     // [0..3] around the launch's kernels (record_ev), [4] behind the copy of
     // the compact-list counters (note_listed): kTimingEvents per call
@@ -100,12 +38,10 @@ struct qd_graph : HostGraph {
     // counters, copied into pinned memory behind the launch), -1 otherwise
     uint64_t* t_listed = nullptr;  // [t_cap][kCmpLists * kCmpSegs], hipHostMalloc
     std::vector<int> t_cmp;
-    // workspace chain: every device-buffer decode records ws_ev on its stream after
-    // its launches; a decode on another stream waits for it first, so the queue and
-    // message scratch of one handle are never used by two streams at once, and a
-    // grow path frees a buffer only after ws_ev (the last use) has completed
-    hipEvent_t ws_ev = nullptr;
-    bool ws_ev_live = false;
+    // workspace chain: every device-buffer decode records it on its stream after
+    // its launches, so the queue and message scratch of one handle are never
+    // used by two streams at once (ws_drain before a grow path frees a buffer)
+    StreamChain ws_chain;
     // 256-B control block: [0] shot-chunk counter of the min-sum wave kernel
     void* ctl = nullptr;
     // qd_graph_set_ssf_stream: SSF kernels of device-buffer decodes go to this
@@ -117,22 +53,12 @@ struct qd_graph : HostGraph {
     // for the SSF kernel of the decode two back on this handle, not the last
     // one: ssf_done[q] is recorded on the SSF stream behind the kernel that
     // used queue q
-    void* qws2 = nullptr;
-    int64_t q2_cap = 0;
+    DevBuf qws2;  // (shots)
     int q_buf = 0;
     hipEvent_t ssf_done[2] = {nullptr, nullptr};
     bool ssf_done_live[2] = {false, false};
-    hipStream_t ws_last = nullptr;
-    // slot scratch of osd_hbm_kernel (grow only; osd_scratch_acquire): one slot per
-    // workgroup, chained over streams through an event of its own
-    void* osd_ws = nullptr;
-    size_t osd_ws_bytes = 0;
-    size_t osd_ws_failed = 0;     // smallest size whose allocation failed (0: none)
-    int64_t osd_slots_cfg = 0;    // qd_osd_set_slots (0: the default)
-    int64_t osd_slots_last = 0;   // slots of the last HBM launch
-    hipEvent_t osd_ev = nullptr;
-    bool osd_ev_live = false;
-    hipStream_t osd_last = nullptr;
+    // slot scratch of osd_hbm_kernel: one slot per workgroup (slots_cfg: qd_osd_set_slots)
+    ChainedSlots osd_ws;
     // kernels the last decode on this handle launched (qd_graph_last_kernels)
     std::string last_bp, last_ssf, last_pre;
     // qd_graph_create_host: tables only, no device, no stream; decodes refuse it
@@ -151,18 +77,10 @@ void set_device(qd_graph* g) {
     if (!g->host_only) hip_check(hipSetDevice(g->device), "hipSetDevice");
 }
 
-// Workspace chain (see qd_graph::ws_ev).
-void ws_acquire(qd_graph* G, hipStream_t s) {
-    if (G->ws_ev_live && G->ws_last != s) hip_check(hipStreamWaitEvent(s, G->ws_ev, 0), "hipStreamWaitEvent");
-}
-void ws_release(qd_graph* G, hipStream_t s) {
-    if (!G->ws_ev) hip_check(hipEventCreateWithFlags(&G->ws_ev, hipEventDisableTiming), "hipEventCreate");
-    hip_check(hipEventRecord(G->ws_ev, s), "hipEventRecord");
-    G->ws_ev_live = true;
-    G->ws_last = s;
-}
+// the last users of the queues, message scratch and unpack buffer: the
+// workspace chain and the SSF kernels of split decodes
 void ws_drain(qd_graph* G) {
-    if (G->ws_ev_live) hip_check(hipEventSynchronize(G->ws_ev), "hipEventSynchronize");
+    G->ws_chain.drain();
     for (int q = 0; q < 2; ++q)
         if (G->ssf_done_live[q]) hip_check(hipEventSynchronize(G->ssf_done[q]), "hipEventSynchronize");
 }
@@ -172,16 +90,10 @@ void ws_drain(qd_graph* G) {
 void attach_queue(qd_graph* G, const DecodePlan& plan, DecodeArgs& a) {
     const DevGraph& g = G->dg;
     if (a.B <= 0 || (!plan.need_queue && !plan.need_lists)) return;
-    if (a.B > G->q_cap) {
-        ws_drain(G);  // launches still in flight may use the old queue
-        if (G->qws) hip_check(hipFree(G->qws), "hipFree queue");
-        G->qws = nullptr;
-        G->q_cap = 0;
-        hip_check(hipMalloc(&G->qws, queue_layout(g, a.B).bytes), "hipMalloc queue");
-        G->q_cap = a.B;
-    }
-    const QueueLayout L = queue_layout(g, G->q_cap);
-    auto* base = static_cast<uint8_t*>(G->qws);
+    if ((size_t)a.B > G->qws.cap)  // launches still in flight may use the old queue
+        G->qws.regrow(a.B, queue_layout(g, a.B).bytes, "hipFree queue", "hipMalloc queue", [&] { ws_drain(G); });
+    const QueueLayout L = queue_layout(g, G->qws.cap);
+    auto* base = static_cast<uint8_t*>(G->qws.p);
     a.q_count = reinterpret_cast<int32_t*>(base);
     a.q_idx = reinterpret_cast<int64_t*>(base + L.idx);
     a.q_x = base + L.x;
@@ -211,17 +123,13 @@ void attach_queue(qd_graph* G, const DecodePlan& plan, DecodeArgs& a) {
 void attach_queue2(qd_graph* G, DecodeArgs& a) {
     if (!a.q_count) return;  // no queue for this launch
     const DevGraph& g = G->dg;
-    if (G->q2_cap < G->q_cap) {
-        ws_drain(G);
-        if (G->qws2) hip_check(hipFree(G->qws2), "hipFree queue 2");
-        G->qws2 = nullptr;
-        G->q2_cap = 0;
-        const QueueLayout L = queue_layout(g, G->q_cap);
-        hip_check(hipMalloc(&G->qws2, g.wave ? L.cmp_count : L.bytes), "hipMalloc queue 2");
-        G->q2_cap = G->q_cap;
+    if (G->qws2.cap < G->qws.cap) {
+        const QueueLayout L = queue_layout(g, G->qws.cap);
+        G->qws2.regrow(G->qws.cap, g.wave ? L.cmp_count : L.bytes, "hipFree queue 2", "hipMalloc queue 2",
+                       [&] { ws_drain(G); });
     }
-    const QueueLayout L = queue_layout(g, G->q2_cap);
-    auto* base = static_cast<uint8_t*>(G->qws2);
+    const QueueLayout L = queue_layout(g, G->qws2.cap);
+    auto* base = static_cast<uint8_t*>(G->qws2.p);
     a.q_count = reinterpret_cast<int32_t*>(base);
     a.q_idx = reinterpret_cast<int64_t*>(base + L.idx);
     a.q_x = base + L.x;
@@ -236,44 +144,9 @@ void flip_counters(qd_graph* G, const DecodeArgs& a, bool triaged) {
 }
 
 void* message_scratch(qd_graph* G, const DecodePlan& plan, const DecodeArgs& a, size_t* bytes) {
-    size_t need = plan.need_scratch ? block_scratch_bytes(G->dg, plan, G->num_cus, a) : 0;
-    *bytes = need;
-    if (need == 0) return nullptr;
-    const size_t floor = block_scratch_floor(G->dg, plan, G->num_cus, a);
-    // capped after an allocation failure: a request at or above the size that
-    // failed keeps the reduced scratch (the launch sizes its grid from the bytes
-    // it gets) instead of draining and failing the same allocation every call
-    // (every 64th such call retries the full size: the memory may be free again)
-    if (need > G->mws_bytes && G->mws && G->mws_failed && need >= G->mws_failed && G->mws_bytes >= floor &&
-        ++G->mws_capped_calls % 64 != 0) {
-        *bytes = G->mws_bytes;
-        return G->mws;
-    }
-    const size_t want = need;
-    if (need > G->mws_bytes) {
-        ws_drain(G);  // launches still in flight may use the old scratch
-        if (G->mws) hip_check(hipFree(G->mws), "hipFree scratch");
-        G->mws = nullptr;
-        G->mws_bytes = 0;
-        // on an allocation failure, halve the slot groups in flight down to one
-        // (the launch sizes its grid from the bytes it gets; results do not change)
-        for (;;) {
-            const hipError_t e = hipMalloc(&G->mws, need);
-            if (e == hipSuccess) {
-                if (need == want) G->mws_failed = 0;  // the full size fits again: no longer capped
-                break;
-            }
-            (void)hipGetLastError();  // clear the sticky error before any launch checks it
-            G->mws = nullptr;
-            if (e != hipErrorOutOfMemory || need <= floor)
-                hip_check(e, "hipMalloc message scratch");
-            G->mws_failed = G->mws_failed ? std::min(G->mws_failed, need) : need;
-            need = std::max(floor, floor + (need - floor) / 2);
-        }
-        G->mws_bytes = need;
-        *bytes = need;
-    }
-    return G->mws;
+    const size_t need = plan.need_scratch ? block_scratch_bytes(G->dg, plan, G->num_cus, a) : 0;
+    HipMem mem([&] { ws_drain(G); });
+    return G->mws.acquire(mem, need, need ? block_scratch_floor(G->dg, plan, G->num_cus, a) : 0, bytes);
 }
 
 // byte rows for a packed decode whose plan expands them (every input the call
@@ -281,15 +154,9 @@ void* message_scratch(qd_graph* G, const DecodePlan& plan, const DecodeArgs& a, 
 void attach_unpack(qd_graph* G, const DecodePlan& plan, DecodeArgs& a) {
     if (!plan.need_unpack) return;
     const size_t need = unpack_region(a.B, G->dg.m) + 2 * unpack_region(a.B, G->dg.n_data) + 256;
-    if (need > G->ubuf_bytes) {
-        ws_drain(G);  // launches in flight may still read the old buffer
-        if (G->ubuf) hip_check(hipFree(G->ubuf), "hipFree unpack buffer");
-        G->ubuf = nullptr;
-        G->ubuf_bytes = 0;
-        hip_check(hipMalloc(&G->ubuf, need), "hipMalloc unpack buffer");
-        G->ubuf_bytes = need;
-    }
-    a.unpack_buf = static_cast<uint8_t*>(G->ubuf);
+    if (need > G->ubuf.cap)  // launches in flight may still read the old buffer
+        G->ubuf.regrow(need, need, "hipFree unpack buffer", "hipMalloc unpack buffer", [&] { ws_drain(G); });
+    a.unpack_buf = static_cast<uint8_t*>(G->ubuf.p);
 }
 
 void check_osd_placement(int32_t placement) {
@@ -297,57 +164,12 @@ void check_osd_placement(int32_t placement) {
         throw Fail(-44, "unknown OSD placement (0 on-chip, 1 HBM, 2 auto)");
 }
 
-// The slot scratch of osd_hbm_kernel for a launch over B shots on `stream`:
-// waits for the handle's last HBM launch when that ran on another stream, grows
-// the scratch when the launch wants more slots than it holds (num_cus *
-// kOsdHbmSlotsPerCu or qd_osd_set_slots, at most B, at most a quarter of the
-// free device memory: -45 when that does not hold one slot), and on an
-// allocation failure halves the slot count down to one (results do not depend
-// on it) before failing with -46.  Returns the slots to launch with.
-int64_t osd_scratch_acquire(qd_graph* G, const OsdHbmLayout& L, int64_t B, hipStream_t stream) {
-    const size_t slot = (size_t)L.slot_bytes;
-    int64_t want = G->osd_slots_cfg > 0 ? G->osd_slots_cfg : (int64_t)G->num_cus * kOsdHbmSlotsPerCu;
-    if (want > B) want = B;
-    if (want < 1) want = 1;
-    if (G->osd_ev_live && G->osd_last != stream) hip_check(hipStreamWaitEvent(stream, G->osd_ev, 0), "hipStreamWaitEvent");
-    int64_t held = (int64_t)(G->osd_ws_bytes / slot);
-    if (want > held && !(held >= 1 && G->osd_ws_failed && (size_t)want * slot >= G->osd_ws_failed)) {
-        size_t free_b = 0, total_b = 0;
-        hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-        const int64_t cap = (int64_t)((free_b + G->osd_ws_bytes) / 4 / slot);  // the scratch held counts as free
-        if (cap < 1)
-            throw Fail(-45, "one OSD slot of " + std::to_string(slot) + " B is beyond the scratch budget (a quarter "
-                            "of the free device memory)");
-        if (want > cap) want = cap;
-    }
-    if (want > held && !(held >= 1 && G->osd_ws_failed && (size_t)want * slot >= G->osd_ws_failed)) {
-        if (G->osd_ev_live) hip_check(hipEventSynchronize(G->osd_ev), "hipEventSynchronize");  // slots may be live
-        if (G->osd_ws) hip_check(hipFree(G->osd_ws), "hipFree OSD scratch");
-        G->osd_ws = nullptr;
-        G->osd_ws_bytes = 0;
-        for (int64_t n = want;; n = (n + 1) / 2) {
-            const hipError_t e = hipMalloc(&G->osd_ws, (size_t)n * slot);
-            if (e == hipSuccess) {
-                G->osd_ws_bytes = (size_t)n * slot;
-                break;
-            }
-            (void)hipGetLastError();  // clear the sticky error before any launch checks it
-            G->osd_ws = nullptr;
-            if (e != hipErrorOutOfMemory) hip_check(e, "hipMalloc OSD scratch");
-            G->osd_ws_failed = G->osd_ws_failed ? std::min(G->osd_ws_failed, (size_t)n * slot) : (size_t)n * slot;
-            if (n == 1) throw Fail(-46, "no memory for one OSD slot of " + std::to_string(slot) + " B");
-        }
-    }
-    held = (int64_t)(G->osd_ws_bytes / slot);
-    return want < held ? want : held;
-}
-
-void osd_scratch_release(qd_graph* G, int64_t slots, hipStream_t stream) {
-    if (!G->osd_ev) hip_check(hipEventCreateWithFlags(&G->osd_ev, hipEventDisableTiming), "hipEventCreate");
-    hip_check(hipEventRecord(G->osd_ev, stream), "hipEventRecord");
-    G->osd_ev_live = true;
-    G->osd_last = stream;
-    G->osd_slots_last = slots;
+// The slot scratch of osd_hbm_kernel: num_cus * kOsdHbmSlotsPerCu slots or
+// qd_osd_set_slots, at most one per shot, within a quarter of the free device
+// memory (-45 when that does not hold one slot); -46 when one slot is refused.
+SlotRule osd_slot_rule(const qd_graph* G, const OsdHbmLayout& L) {
+    return {(size_t)L.slot_bytes, (int64_t)G->num_cus * kOsdHbmSlotsPerCu, -46, "no memory for one OSD slot of ",
+            -45, "one OSD slot of ", "hipMalloc OSD scratch", "hipFree OSD scratch"};
 }
 
 void note_kernels(qd_graph* G) {
@@ -469,7 +291,7 @@ void enqueue_decode(qd_graph* G, const qd_params* p, DecodeArgs& a, hipStream_t 
         if (qb == 1) attach_queue2(G, a);
         a.wave_ctr = static_cast<unsigned long long*>(G->ctl) + 32 * qb;
     }
-    ws_acquire(G, s);
+    G->ws_chain.acquire(s);
     // an SSF kernel still running on the SSF stream must have finished before
     // its queue and control words are reset: a split decode reuses those of the
     // split decode two back on this handle (queue qb); an unsplit one uses queue
@@ -492,7 +314,7 @@ void enqueue_decode(qd_graph* G, const qd_params* p, DecodeArgs& a, hipStream_t 
     }
     // the workspace chain (message scratch, compact lists, counters) ends with
     // the BP stage; the SSF queues are ordered by ssf_done
-    ws_release(G, s);
+    G->ws_chain.release(s);
 }
 
 // Both graph constructors: validate the CSR, then build every graph table into
@@ -681,10 +503,10 @@ int qd_graph_hgp_decode_bp(qd_graph* G, int64_t B, const uint8_t* syn, uint8_t* 
         a.max_iter = max_iter;
         a.ms_scaling = ms_scaling;
         hipStream_t st = stream ? static_cast<hipStream_t>(stream) : G->stream;
-        ws_acquire(G, st);
+        G->ws_chain.acquire(st);
         if (hgp_launch_bp(P, a, st) != 0) throw Fail(-94, "HGP kernel launch failed");
         hip_check(hipGetLastError(), "HGP kernel");
-        ws_release(G, st);
+        G->ws_chain.release(st);
     });
 }
 
@@ -698,7 +520,7 @@ int qd_graph_destroy(qd_graph* g) {
         }
         (void)hipSetDevice(g->device);
         if (g->stream) (void)hipStreamSynchronize(g->stream);
-        if (g->ws_ev_live) (void)hipEventSynchronize(g->ws_ev);
+        g->ws_chain.destroy();  // waits first; free_timing's drain is then a no-op
         for (int q = 0; q < 2; ++q)
             if (g->ssf_done[q]) {
                 if (g->ssf_done_live[q]) (void)hipEventSynchronize(g->ssf_done[q]);
@@ -706,18 +528,11 @@ int qd_graph_destroy(qd_graph* g) {
                 g->ssf_done[q] = nullptr;
                 g->ssf_done_live[q] = false;
             }
-        if (g->qws2) (void)hipFree(g->qws2);
-        if (g->ws_ev) (void)hipEventDestroy(g->ws_ev);
-        g->ws_ev = nullptr;
-        g->ws_ev_live = false;  // drained above (free_timing's drain is a no-op)
+        if (g->qws2.p) (void)hipFree(g->qws2.p);
         if (g->ssf_ev) (void)hipEventDestroy(g->ssf_ev);
-        if (g->ws) (void)hipFree(g->ws);
-        if (g->qws) (void)hipFree(g->qws);
-        if (g->mws) (void)hipFree(g->mws);
-        if (g->ubuf) (void)hipFree(g->ubuf);
-        if (g->osd_ev_live) (void)hipEventSynchronize(g->osd_ev);  // an HBM OSD launch may still use its slots
-        if (g->osd_ev) (void)hipEventDestroy(g->osd_ev);
-        if (g->osd_ws) (void)hipFree(g->osd_ws);
+        for (void* p : {g->ws.p, g->qws.p, g->mws.ptr, g->ubuf.p})
+            if (p) (void)hipFree(p);
+        g->osd_ws.destroy();  // an HBM OSD launch may still use its slots
         if (g->cmpc) (void)hipFree(g->cmpc);
         if (g->ctl) (void)hipFree(g->ctl);
         hgp_plan_destroy(g->hgp);
@@ -810,14 +625,10 @@ int qd_decode_batch(qd_graph* G, const qd_params* p, int64_t B, const uint8_t* s
         const Reg r_st = reg((size_t)B, status != nullptr);
         const Reg r_ss = reg((size_t)B * 4, ssf_steps != nullptr);
         const Reg r_fl = reg((size_t)B, fail != nullptr);
-        if (off > G->ws_bytes) {
-            if (G->ws) hip_check(hipFree(G->ws), "hipFree");
-            G->ws = nullptr;
-            G->ws_bytes = 0;
-            hip_check(hipMalloc(&G->ws, off), "hipMalloc workspace");
-            G->ws_bytes = off;
-        }
-        auto* w = static_cast<uint8_t*>(G->ws);
+        // no drain: every call of this entry point ends in a stream synchronise,
+        // so the workspace has no user left
+        if (off > G->ws.cap) G->ws.regrow(off, off, "hipFree", "hipMalloc workspace", [] {});
+        auto* w = static_cast<uint8_t*>(G->ws.p);
         auto dptr = [&](const Reg& r) -> void* { return r.bytes ? (void*)(w + r.off) : nullptr; };
         hipStream_t s = G->stream;
         if (syn) hip_check(hipMemcpyAsync(dptr(r_syn), syn, r_syn.bytes, hipMemcpyHostToDevice, s), "H2D syn");
@@ -969,9 +780,9 @@ int qd_osd_batch_device_placed(qd_graph* G, int32_t method, int32_t order, int64
         if (pl.kernel != kOsdHbm) {
             rc = launch_osd(G->dg, a, G->num_cus, (hipStream_t)stream);
         } else {
-            const int64_t slots = osd_scratch_acquire(G, pl.L, B, (hipStream_t)stream);
-            rc = launch_osd_hbm(G->dg, a, G->osd_ws, slots, (hipStream_t)stream);
-            osd_scratch_release(G, slots, (hipStream_t)stream);
+            const int64_t slots = G->osd_ws.acquire(osd_slot_rule(G, pl.L), B, (hipStream_t)stream);
+            rc = launch_osd_hbm(G->dg, a, G->osd_ws.ptr, slots, (hipStream_t)stream);
+            G->osd_ws.release(slots, (hipStream_t)stream);
         }
         if (rc != 0) throw Fail(-104, std::string("osd launch failed: ") + hipGetErrorString((hipError_t)rc));
     });
@@ -1001,7 +812,7 @@ int qd_osd_set_slots(qd_graph* G, int64_t slots) {
     return guarded([&] {
         check_graph(G);
         if (slots < 0 || slots > (1ll << 20)) throw Fail(-47, "osd slots must be 0 (default) .. 2^20");
-        G->osd_slots_cfg = slots;
+        G->osd_ws.slots_cfg = slots;
     });
 }
 
@@ -1011,8 +822,8 @@ int qd_osd_hbm_info(const qd_graph* G, int64_t out[3]) {
         if (!out) throw Fail(-83, "null output");
         OsdHbmLayout L;
         out[0] = osd_hbm_choose(G->dg, &L) ? L.slot_bytes : 0;
-        out[1] = G->osd_slots_last;
-        out[2] = (int64_t)G->osd_ws_bytes;
+        out[1] = G->osd_ws.slots_last;
+        out[2] = (int64_t)G->osd_ws.bytes;
     });
 }
 
@@ -1299,291 +1110,6 @@ int qd_count_flags_device(const uint8_t* flags, int64_t B, uint8_t mask, int64_t
         if (B < 0 || (B > 0 && (!flags || !out))) throw Fail(-70, "invalid count arguments");
         const int rc = launch_count_flags(flags, B, mask, out, (hipStream_t)stream);
         if (rc != 0) throw Fail(-103, std::string("count launch failed: ") + hipGetErrorString((hipError_t)rc));
-    });
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- compiled circuits
-// A validated Pauli-frame program (qdec_circuit.h) and, unless host-only, its
-// copy on one device.
-struct qd_circuit {
-    HostCircuit hc;
-    DevCircuit dc{};
-    bool host_only = true;
-    int device = 0;
-    int num_cus = 0;
-    DeviceSink arena;
-    // where the kernels keep the frame: FP_LDS or FP_HBM (FP_AUTO is resolved at create)
-    int32_t placement = FP_LDS;
-    // HBM placement: the handle's slot scratch.  Every launch records fws_ev on its
-    // stream behind the kernel and a launch on another stream waits for it first
-    // (the chain of qd_graph::ws_ev), so two calls never share live slots; the
-    // scratch is freed or regrown only after fws_ev has completed.
-    void* fws = nullptr;
-    size_t fws_bytes = 0;
-    size_t fws_failed = 0;    // smallest request hipMalloc refused (0: none): not asked for again
-    int64_t slots_cfg = 0;    // qd_circuit_set_frame_slots; 0: num_cus * kFrameHbmSlotsPerCu
-    int64_t slots_last = 0;   // slots of the last launch
-    hipEvent_t fws_ev = nullptr;
-    bool fws_ev_live = false;
-    hipStream_t fws_last = nullptr;
-};
-
-namespace {
-
-int create_circuit(int32_t placement, bool host_only, int32_t device, int32_t num_qubits, int32_t n_ops,
-                   const int32_t* ops, int32_t n_targets, const int32_t* targets, const double* probs,
-                   int32_t n_groups, const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
-                   qd_circuit** out, int32_t n_args = -1, const double* args = nullptr) {
-    return guarded([&] {
-        if (!out) throw Fail(-71, "circuit: null output handle");
-        *out = nullptr;
-        if (placement != FP_LDS && placement != FP_HBM && placement != FP_AUTO)
-            throw Fail(-96, "circuit: unknown frame placement (0 LDS, 1 HBM, 2 auto)");
-        std::unique_ptr<qd_circuit> C(new qd_circuit());
-        build_circuit(C->hc, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows, row_ptr,
-                      rec_idx, placement != FP_LDS, n_args, args);
-        C->placement = placement == FP_AUTO ? (C->hc.lds_bytes > kFrameLdsLimit ? FP_HBM : FP_LDS) : placement;
-        C->host_only = host_only;
-        const HostCircuit& h = C->hc;
-        DevCircuit& d = C->dc;
-        d.Q = h.Q, d.M = h.M, d.n_ops = (int32_t)h.ops.size();
-        for (int g = 0; g < kFrameGroups; ++g) d.rows[g] = h.rows[g], d.row_off[g] = h.row_off[g];
-        if (!host_only) {
-            int ndev = 0;
-            hip_check(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
-            if (device < 0 || device >= ndev) throw Fail(-15, "device ordinal out of range");
-            C->device = device;
-            hip_check(hipSetDevice(device), "hipSetDevice");
-            hipDeviceProp_t prop;
-            hip_check(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties");
-            C->num_cus = prop.multiProcessorCount;
-            d.ops = static_cast<const FrameOpRec*>(C->arena.put(h.ops.data(), h.ops.size() * sizeof(FrameOpRec)));
-            d.targets = static_cast<const int32_t*>(C->arena.put(h.targets.data(), h.targets.size() * 4));
-            d.cum = static_cast<const uint32_t*>(C->arena.put(h.cum.data(), h.cum.size() * 4));
-            d.row_ptr = static_cast<const int32_t*>(C->arena.put(h.row_ptr.data(), h.row_ptr.size() * 4));
-            d.rec_idx = static_cast<const int32_t*>(C->arena.put(h.rec_idx.data(), h.rec_idx.size() * 4));
-        }
-        *out = C.release();
-    });
-}
-
-// The slot scratch of an HBM-placed handle for a launch over `words` 64-shot
-// words on `stream`: waits for the handle's last launch when that ran on another
-// stream, grows the scratch when the launch wants more slots than it holds, and
-// on an allocation failure halves the slot count down to one (results do not
-// depend on it) before failing with -97.  Returns the slots to launch with.
-int64_t frame_scratch_acquire(qd_circuit* C, int64_t words, hipStream_t stream) {
-    const size_t slot = C->hc.lds_bytes;
-    int64_t want = C->slots_cfg > 0 ? C->slots_cfg : (int64_t)C->num_cus * kFrameHbmSlotsPerCu;
-    if (want > words) want = words;
-    if (want < 1) want = 1;
-    if (C->fws_ev_live && C->fws_last != stream) hip_check(hipStreamWaitEvent(stream, C->fws_ev, 0), "hipStreamWaitEvent");
-    const int64_t held = (int64_t)(C->fws_bytes / slot);
-    if (want > held && !(held >= 1 && C->fws_failed && (size_t)want * slot >= C->fws_failed)) {
-        if (C->fws_ev_live) hip_check(hipEventSynchronize(C->fws_ev), "hipEventSynchronize");  // slots may be live
-        if (C->fws) hip_check(hipFree(C->fws), "hipFree frame scratch");
-        C->fws = nullptr;
-        C->fws_bytes = 0;
-        for (int64_t n = want;; n = (n + 1) / 2) {
-            const hipError_t e = hipMalloc(&C->fws, (size_t)n * slot);
-            if (e == hipSuccess) {
-                C->fws_bytes = (size_t)n * slot;
-                break;
-            }
-            (void)hipGetLastError();  // clear the sticky error before any launch checks it
-            C->fws = nullptr;
-            if (e != hipErrorOutOfMemory) hip_check(e, "hipMalloc frame scratch");
-            C->fws_failed = C->fws_failed ? std::min(C->fws_failed, (size_t)n * slot) : (size_t)n * slot;
-            if (n == 1)
-                throw Fail(-97, "circuit: no memory for one frame slot of " + std::to_string(slot) + " B");
-        }
-    }
-    const int64_t have = (int64_t)(C->fws_bytes / slot);
-    return want < have ? want : have;
-}
-
-void frame_scratch_release(qd_circuit* C, int64_t slots, hipStream_t stream) {
-    if (!C->fws_ev) hip_check(hipEventCreateWithFlags(&C->fws_ev, hipEventDisableTiming), "hipEventCreate");
-    hip_check(hipEventRecord(C->fws_ev, stream), "hipEventRecord");
-    C->fws_ev_live = true;
-    C->fws_last = stream;
-    C->slots_last = slots;
-}
-
-// The output list of a sampler / fault call (`what`) against the handle: -77 for
-// a null list or a group the circuit lacks, -78 for a misaligned packed row.
-// Copies the pointers to o; true when flags ask for packed rows (the callers
-// refuse unknown flags where their own order of checks has it).
-bool frame_outs(const qd_circuit* C, const char* what, int32_t flags, void* const outs[4], void* (&o)[kFrameGroups]) {
-    if (!outs) throw Fail(-77, std::string("invalid circuit ") + what + " arguments: null output list");
-    const bool packed = (flags & QD_INPUT_PACKED) != 0;
-    for (int g = 0; g < kFrameGroups; ++g) {
-        o[g] = outs[g];
-        if (o[g] && g >= C->hc.n_groups) throw Fail(-77, "output buffer for a group the circuit does not have");
-        if (packed && ((uintptr_t)o[g] & 7)) throw Fail(-78, "packed rows must be 8-B aligned");
-    }
-    return packed;
-}
-
-// One launch over `words` 64-shot (64-fault) words on the handle's placement: in
-// HBM between the acquire and the release of its slot scratch.  -102 with the
-// caller's wording (`what`) when launch(place) does not return 0.
-template <class Launch>
-void frame_launch(qd_circuit* C, const char* what, int64_t words, hipStream_t stream, Launch&& launch) {
-    hip_check(hipSetDevice(C->device), "hipSetDevice");
-    const bool hbm = C->placement == FP_HBM;
-    FramePlace at;
-    at.placement = C->placement, at.lds = at.slot_bytes = C->hc.lds_bytes, at.num_cus = C->num_cus;
-    if (hbm) at.slots = frame_scratch_acquire(C, words, stream), at.scratch = C->fws;
-    const int rc = launch(at);
-    if (hbm) frame_scratch_release(C, at.slots, stream);
-    if (rc != 0) throw Fail(-102, std::string(what) + " launch failed: " + hipGetErrorString((hipError_t)rc));
-}
-
-}  // namespace
-
-extern "C" {
-
-int qd_circuit_create(int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
-                      const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
-                      const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out) {
-    return create_circuit(FP_LDS, false, device, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
-                          group_rows, row_ptr, rec_idx, out);
-}
-
-int qd_circuit_create_host(int32_t num_qubits, int32_t n_ops, const int32_t* ops, int32_t n_targets,
-                           const int32_t* targets, const double* probs, int32_t n_groups, const int32_t* group_rows,
-                           const int32_t* row_ptr, const int32_t* rec_idx, qd_circuit** out) {
-    return create_circuit(FP_LDS, true, 0, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups, group_rows,
-                          row_ptr, rec_idx, out);
-}
-
-int qd_circuit_create_placed(int32_t placement, int32_t device, int32_t num_qubits, int32_t n_ops,
-                             const int32_t* ops, int32_t n_targets, const int32_t* targets, const double* probs,
-                             int32_t n_groups, const int32_t* group_rows, const int32_t* row_ptr,
-                             const int32_t* rec_idx, qd_circuit** out) {
-    return create_circuit(placement, false, device, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
-                          group_rows, row_ptr, rec_idx, out);
-}
-
-int qd_circuit_create_host_placed(int32_t placement, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
-                                  int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
-                                  const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
-                                  qd_circuit** out) {
-    return create_circuit(placement, true, 0, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
-                          group_rows, row_ptr, rec_idx, out);
-}
-
-int qd_circuit_create_args(int32_t placement, int32_t device, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
-                           int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
-                           const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx, int32_t n_args,
-                           const double* args, qd_circuit** out) {
-    if (n_args < 0) return guarded([] { throw Fail(-71, "circuit: negative argument count"); });
-    return create_circuit(placement, false, device, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
-                          group_rows, row_ptr, rec_idx, out, n_args, args);
-}
-
-int qd_circuit_create_host_args(int32_t placement, int32_t num_qubits, int32_t n_ops, const int32_t* ops,
-                                int32_t n_targets, const int32_t* targets, const double* probs, int32_t n_groups,
-                                const int32_t* group_rows, const int32_t* row_ptr, const int32_t* rec_idx,
-                                int32_t n_args, const double* args, qd_circuit** out) {
-    if (n_args < 0) return guarded([] { throw Fail(-71, "circuit: negative argument count"); });
-    return create_circuit(placement, true, 0, num_qubits, n_ops, ops, n_targets, targets, probs, n_groups,
-                          group_rows, row_ptr, rec_idx, out, n_args, args);
-}
-
-int qd_circuit_set_frame_slots(qd_circuit* C, int64_t slots) {
-    return guarded([&] {
-        if (!C) throw Fail(-71, "circuit: null handle");
-        if (slots < 0 || slots > (1ll << 20)) throw Fail(-98, "circuit: frame slots must be 0 (default) .. 2^20");
-        C->slots_cfg = slots;
-    });
-}
-
-int qd_circuit_frame_info(const qd_circuit* C, int64_t out[4]) {
-    return guarded([&] {
-        if (!C || !out) throw Fail(-71, "circuit: null handle or output");
-        out[0] = C->placement, out[1] = (int64_t)C->hc.lds_bytes, out[2] = C->slots_last;
-        out[3] = (int64_t)C->fws_bytes;
-    });
-}
-
-int qd_circuit_op_flags_copy(const qd_circuit* C, int32_t* dup) {
-    return guarded([&] {
-        if (!C || (!dup && !C->hc.ops.empty())) throw Fail(-71, "circuit: null handle or output");
-        for (size_t i = 0; i < C->hc.ops.size(); ++i) dup[i] = C->hc.ops[i].dup;
-    });
-}
-
-int qd_circuit_destroy(qd_circuit* C) {
-    return guarded([&] {
-        if (!C) return;
-        if (!C->host_only) (void)hipSetDevice(C->device);
-        if (C->fws_ev_live) (void)hipEventSynchronize(C->fws_ev);  // a launch may still use the slots
-        if (C->fws) (void)hipFree(C->fws);
-        if (C->fws_ev) (void)hipEventDestroy(C->fws_ev);
-        delete C;  // its sink frees the uploads
-    });
-}
-
-int qd_circuit_info(const qd_circuit* C, int64_t out[10]) {
-    return guarded([&] {
-        if (!C || !out) throw Fail(-71, "circuit: null handle or output");
-        const HostCircuit& h = C->hc;
-        out[0] = h.Q, out[1] = h.M;
-        for (int g = 0; g < kFrameGroups; ++g) out[2 + g] = h.rows[g];
-        out[6] = (int64_t)h.lds_bytes, out[7] = (int64_t)h.ops.size(), out[8] = h.n_sites, out[9] = h.n_rsites;
-    });
-}
-
-int qd_circuit_sample_device(qd_circuit* C, uint32_t seed, uint32_t stream_id, int64_t shot0, int64_t B,
-                             int32_t flags, void* const outs[4], void* stream) {
-    return guarded([&] {
-        if (!C) throw Fail(-71, "circuit: null handle");
-        if (C->host_only) throw Fail(-79, "host-only circuit (qd_circuit_create_host): no device to sample on");
-        if (B < 0 || (flags & ~QD_INPUT_PACKED)) throw Fail(-77, "invalid circuit sampler arguments");
-        if (B == 0) return;
-        void* o[kFrameGroups];
-        const bool packed = frame_outs(C, "sampler", flags, outs, o);
-        frame_launch(C, "sampler", (B + 63) / 64, (hipStream_t)stream, [&](const FramePlace& at) {
-            return launch_frame_sample(C->dc, at, seed, stream_id, shot0, B, packed, o, (hipStream_t)stream);
-        });
-    });
-}
-
-int qd_circuit_fault_info(const qd_circuit* C, int64_t out[4]) {
-    return guarded([&] {
-        if (!C || !out) throw Fail(-71, "circuit: null handle or output");
-        out[0] = fault_total(C->hc, 0), out[1] = fault_total(C->hc, 1), out[2] = out[3] = 0;
-    });
-}
-
-int qd_circuit_fault_table(const qd_circuit* C, int32_t kind, int32_t* op, int32_t* target, int32_t* comp) {
-    return guarded([&] {
-        if (!C) throw Fail(-71, "circuit: null handle");
-        circuit_fault_table(C->hc, kind, op, target, comp);
-    });
-}
-
-int qd_circuit_faults_device(qd_circuit* C, int32_t kind, int64_t f0, int64_t F, int32_t flags, void* const outs[4],
-                             void* stream) {
-    return guarded([&] {
-        if (!C) throw Fail(-71, "circuit: null handle");
-        if (kind != 0 && kind != 1) throw Fail(-87, "circuit faults: kind must be 0 (noise) or 1 (gauge)");
-        if (f0 < 0 || F < 0) throw Fail(-88, "circuit faults: negative first fault or count");
-        if (F > (int64_t)fault_total(C->hc, kind) - f0)
-            throw Fail(-89, "circuit faults: window beyond the circuit's " +
-                                std::to_string(fault_total(C->hc, kind)) + " faults of this kind");
-        if (flags & ~QD_INPUT_PACKED) throw Fail(-77, "invalid circuit fault arguments: unknown flags");
-        if (C->host_only) throw Fail(-79, "host-only circuit (qd_circuit_create_host): no device to propagate on");
-        if (F == 0) return;
-        void* o[kFrameGroups];
-        const bool packed = frame_outs(C, "fault", flags, outs, o);
-        frame_launch(C, "fault", (F + 63) / 64, (hipStream_t)stream, [&](const FramePlace& at) {
-            return launch_frame_faults(C->dc, at, kind, (int32_t)f0, (int32_t)F, packed, o, (hipStream_t)stream);
-        });
     });
 }
 

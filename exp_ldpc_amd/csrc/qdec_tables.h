@@ -2,7 +2,7 @@
 // slot tables for the wave kernels, the LDS layouts, flip-set tables for SSF,
 // bit-packed logicals, priors in both precisions, the queue layout.  Pure host
 // code with no HIP header: every table goes through a TableSink, which the
-// library backs with device memory (qdec_abi.cpp) and a host-only graph or a
+// library backs with device memory (qdec_abi.h) and a host-only graph or a
 // stand-alone checker (tools/tables_check.cpp) with plain host copies.
 #pragma once
 #include <stdint.h>
