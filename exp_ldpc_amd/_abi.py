@@ -28,6 +28,7 @@ QD_SYN_ADD_BASE, QD_SYN_ADD_READOUT = 1, 2
 QD_INPUT_PACKED = 16  # bit-packed input rows (include/qdec.h)
 QD_ST_BP_CONVERGED, QD_ST_SATISFIED = 1, 2
 QD_OSD_ONCHIP, QD_OSD_HBM, QD_OSD_AUTO = 0, 1, 2  # where the device OSD keeps its rows
+QD_RELAY_LDS, QD_RELAY_HBM, QD_RELAY_AUTO = 0, 1, 2  # where the relay stage keeps its messages
 
 
 class QdParams(C.Structure):
@@ -39,6 +40,18 @@ class QdParams(C.Structure):
         ("ssf_max_steps", C.c_int32),
         ("syn_flags", C.c_int32),
         ("ms_scaling", C.c_double),
+    ]
+
+
+class QdRelayParams(C.Structure):
+    _fields_ = [
+        ("gamma0", C.c_double),
+        ("alpha", C.c_double),
+        ("clip", C.c_double),
+        ("pre_iter", C.c_int32),
+        ("num_sets", C.c_int32),
+        ("set_max_iter", C.c_int32),
+        ("stop_nconv", C.c_int32),
     ]
 
 
@@ -109,6 +122,12 @@ SIGNATURES = {
     "qd_osd_kernel_info_placed": (_i32, [_p, _i32, _p]),
     "qd_osd_set_slots": (_i32, [_p, _i64]),
     "qd_osd_hbm_info": (_i32, [_p, _p]),
+    "qd_graph_set_relay": (_i32, [_p, C.POINTER(QdRelayParams), _p]),
+    "qd_relay_batch_device": (_i32, [_p, _i32, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _p]),
+    "qd_relay_batch": (_i32, [_p, _i32, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32]),
+    "qd_relay_set_slots": (_i32, [_p, _i64]),
+    "qd_relay_info": (_i32, [_p, _i32, _i32, _p]),
+    "qd_relay_kernel_names": (_i64, [C.c_char_p, _i64]),
     "qd_graph_set_option": (_i32, [_p, _i32, _i32]),
     "qd_graph_get_option": (_i32, [_p, _i32, C.POINTER(_i32)]),
     "qd_graph_ssf_tables": (_i32, [_p, C.POINTER(_i32), C.POINTER(_i64)]),

@@ -59,6 +59,18 @@ struct qd_graph : HostGraph {
     bool ssf_done_live[2] = {false, false};
     // slot scratch of osd_hbm_kernel: one slot per workgroup (slots_cfg: qd_osd_set_slots)
     ChainedSlots osd_ws;
+    // relay stage (qd_graph_set_relay): the caller's parameters and strengths, kept
+    // to rebuild the tables when the priors change; the tables (relay_ok: built
+    // from BP priors); the slot scratch of the HBM placement, whose chain orders
+    // the launches of both placements (slots_cfg: qd_relay_set_slots); and the
+    // launches' shot counter
+    bool relay_set = false, relay_ok = false;
+    RelayParams relay_p{};
+    std::vector<double> relay_gammas;
+    std::unique_ptr<TableSink> relay_arena;
+    RelayTables relay_t{};
+    ChainedSlots relay_ws;
+    void* relay_ctr = nullptr;
     // kernels the last decode on this handle launched (qd_graph_last_kernels)
     std::string last_bp, last_ssf, last_pre;
     // qd_graph_create_host: tables only, no device, no stream; decodes refuse it
@@ -170,6 +182,35 @@ void check_osd_placement(int32_t placement) {
 SlotRule osd_slot_rule(const qd_graph* G, const OsdHbmLayout& L) {
     return {(size_t)L.slot_bytes, (int64_t)G->num_cus * kOsdHbmSlotsPerCu, -46, "no memory for one OSD slot of ",
             -45, "one OSD slot of ", "hipMalloc OSD scratch", "hipFree OSD scratch"};
+}
+
+void check_relay_placement(int32_t placement) {
+    if (placement != QD_RELAY_LDS && placement != QD_RELAY_HBM && placement != QD_RELAY_AUTO)
+        throw Fail(-55, "unknown relay placement (0 LDS, 1 HBM, 2 auto)");
+}
+
+// The relay tables from the kept parameters and the current priors; a launch in
+// flight may still read the old ones.
+void build_relay(qd_graph* G) {
+    if (!G->host_only) G->relay_ws.chain.drain();
+    G->relay_arena->release();
+    G->relay_ok = false;
+    if (!G->bp_priors) return;
+    const RelayParams& p = G->relay_p;
+    const RelayHostTables t = relay_build_tables(p, G->relay_gammas.data(), G->dg.n, G->prior_ms64.data());
+    RelayTables& rt = G->relay_t;
+    rt.gamma[QD_F64] = G->relay_arena->upload(t.g64);
+    rt.gamma[QD_F32] = G->relay_arena->upload(t.g32);
+    rt.w = G->relay_arena->upload(t.w);
+    rt.pre_iter = p.pre_iter, rt.num_sets = p.num_sets, rt.set_max_iter = p.set_max_iter;
+    rt.stop_nconv = p.stop_nconv, rt.alpha = p.alpha, rt.clip = p.clip;
+    G->relay_ok = true;
+}
+
+// the default grid with the messages in LDS: what a CU's LDS holds, at most kRelayLdsPerCu
+int64_t relay_lds_grid(const qd_graph* G, const RelayLayout& L) {
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kRelayLdsPerCu, (int64_t)kRelayLdsMax / L.lds_bytes(false)));
+    return G->relay_ws.slots_cfg > 0 ? G->relay_ws.slots_cfg : (int64_t)G->num_cus * per_cu;
 }
 
 void note_kernels(qd_graph* G) {
@@ -357,6 +398,8 @@ int create_graph(int32_t m, int32_t n, const int32_t* row_ptr, const int32_t* co
                 if (host_only) sink->reset(new HostSink());
                 else sink->reset(new DeviceSink());
             }
+            if (host_only) G->relay_arena.reset(new HostSink());
+            else G->relay_arena.reset(new DeviceSink());
             init_graph(G, m, n, row_ptr, col_idx, n_data, fold_blocks);
         } catch (...) {
             if (G->stream) (void)hipStreamDestroy(G->stream);
@@ -533,6 +576,8 @@ int qd_graph_destroy(qd_graph* g) {
         for (void* p : {g->ws.p, g->qws.p, g->mws.ptr, g->ubuf.p})
             if (p) (void)hipFree(p);
         g->osd_ws.destroy();  // an HBM OSD launch may still use its slots
+        g->relay_ws.destroy();
+        if (g->relay_ctr) (void)hipFree(g->relay_ctr);
         if (g->cmpc) (void)hipFree(g->cmpc);
         if (g->ctl) (void)hipFree(g->ctl);
         hgp_plan_destroy(g->hgp);
@@ -575,6 +620,7 @@ int qd_graph_set_priors(qd_graph* G, const double* probs) {
         set_priors(G, probs);  // on a throw the previous tables and flags stand
         G->has_priors = G->bp_priors;
         G->has_thr = true;
+        if (G->relay_set) build_relay(G);
     });
 }
 
@@ -824,6 +870,168 @@ int qd_osd_hbm_info(const qd_graph* G, int64_t out[3]) {
         out[0] = osd_hbm_choose(G->dg, &L) ? L.slot_bytes : 0;
         out[1] = G->osd_ws.slots_last;
         out[2] = (int64_t)G->osd_ws.bytes;
+    });
+}
+
+int qd_graph_set_relay(qd_graph* G, const qd_relay_params* prm, const double* gammas) {
+    static_assert(sizeof(qd_relay_params) == sizeof(RelayParams), "qd_relay_params and RelayParams");
+    return guarded([&] {
+        check_graph(G);
+        const RelayParams* p = reinterpret_cast<const RelayParams*>(prm);
+        relay_check_params(p, gammas, G->dg.n);
+        if (!G->has_priors && G->has_thr)
+            throw Fail(-51, "the graph's priors hold a 0 or a 1: relay needs probabilities inside (0, 1)");
+        if (!G->has_priors) throw Fail(-5, "priors not set (qd_graph_set_priors)");
+        set_device(G);
+        G->relay_p = *p;
+        G->relay_gammas.assign(gammas, gammas + (gammas ? (size_t)p->num_sets * G->dg.n : 0));
+        G->relay_set = true;
+        build_relay(G);
+    });
+}
+
+int qd_relay_set_slots(qd_graph* G, int64_t slots) {
+    return guarded([&] {
+        check_graph(G);
+        if (slots < 0 || slots > kRelayMaxSlots) throw Fail(-52, "relay slots must be 0 (default) .. 2^20");
+        G->relay_ws.slots_cfg = slots;
+    });
+}
+
+int qd_relay_info(const qd_graph* G, int32_t precision, int32_t placement, int64_t out[4]) {
+    return guarded([&] {
+        check_graph(G);
+        if (precision != QD_F32 && precision != QD_F64) throw Fail(-4, "unknown precision");
+        check_relay_placement(placement);
+        if (!out) throw Fail(-52, "null output");
+        const RelayLayout L(G->dg, precision == QD_F32 ? 4 : 8);
+        const int kind = relay_place(L, placement);
+        if (kind < 0) throw Fail(-56, "graph too large for this relay placement (LDS above 160 KiB)");
+        out[0] = kind;
+        out[1] = L.lds_bytes(kind == QD_RELAY_HBM);
+        out[2] = kind == QD_RELAY_HBM ? L.slot_bytes : 0;
+        out[3] = G->relay_ws.slots_last;
+    });
+}
+
+int64_t qd_relay_kernel_names(char* buf, int64_t cap) {
+    int64_t len = 0;
+    const int e = guarded([&] {
+        std::string s;
+        append_relay_kernel_names(s);
+        len = (int64_t)s.size();
+        if (buf && cap > 0) {
+            const size_t k = std::min<size_t>(s.size(), (size_t)cap - 1);
+            std::memcpy(buf, s.data(), k);
+            buf[k] = 0;
+        }
+    });
+    return e ? e : len;
+}
+
+// the checks both relay entry points share, in the order qdec.h lists them;
+// false: B = 0, nothing to do
+static bool check_relay_call(const qd_graph* G, int32_t precision, int64_t B, const uint8_t* syn, int32_t syn_flags,
+                             const uint8_t* base, const uint8_t* readout, const uint8_t* fail, int32_t placement,
+                             RelayLayout* L, int* kind) {
+    check_graph(G);
+    if (precision != QD_F32 && precision != QD_F64) throw Fail(-4, "unknown precision");
+    if (B < 0) throw Fail(-8, "negative batch");
+    check_relay_placement(placement);
+    if (syn_flags & QD_INPUT_PACKED) throw Fail(-57, "the relay stage takes byte rows (QD_INPUT_PACKED refused)");
+    if (syn_flags & ~3) throw Fail(-57, "unknown syn_flags");
+    if (fail && readout && G->dg.k > 0 && (G->dg.k > 256 || !G->dg.lz))
+        throw Fail(-57, "fused failure check after relay supports <= 256 logicals");
+    if (!G->relay_set) throw Fail(-54, "relay tables not set (qd_graph_set_relay)");
+    if (!G->has_priors && G->has_thr)
+        throw Fail(-51, "the graph's priors hold a 0 or a 1: relay needs probabilities inside (0, 1)");
+    if (!G->has_priors || !G->relay_ok) throw Fail(-5, "priors not set (qd_graph_set_priors)");
+    if (B == 0) return false;
+    if (!syn && !(syn_flags && (base || readout))) throw Fail(-7, "no syndrome source");
+    *L = RelayLayout(G->dg, precision == QD_F32 ? 4 : 8);
+    *kind = relay_place(*L, placement);
+    if (*kind < 0) throw Fail(-56, "graph too large for this relay placement (LDS above 160 KiB)");
+    if (G->host_only) throw Fail(-16, "host-only graph (qd_graph_create_host): no device to run relay on");
+    return true;
+}
+
+static void enqueue_relay(qd_graph* G, int32_t precision, const RelayArgs& args, const RelayLayout& L, int kind,
+                          hipStream_t s) {
+    RelayArgs a = args;
+    int64_t grid;
+    void* scr = nullptr;
+    if (kind == QD_RELAY_HBM) {
+        grid = G->relay_ws.acquire(relay_slot_rule((size_t)L.slot_bytes, (int64_t)G->num_cus * kRelaySlotsPerCu), a.B, s);
+        scr = G->relay_ws.ptr;
+    } else {  // no slots, but the shot counter is the handle's: the same chain
+        G->relay_ws.chain.acquire(s);
+        grid = std::min(relay_lds_grid(G, L), a.B);
+    }
+    if (!G->relay_ctr) hip_check(hipMalloc(&G->relay_ctr, 256), "hipMalloc relay counter");
+    a.work_ctr = static_cast<unsigned long long*>(G->relay_ctr);
+    hip_check(hipMemsetAsync(a.work_ctr, 0, sizeof(unsigned long long), s), "hipMemsetAsync relay counter");
+    const int rc = launch_relay(G->dg, precision, a, G->relay_t, L, scr, grid, s);
+    G->relay_ws.release(grid, s);
+    if (rc != 0) throw Fail(-105, std::string("relay launch failed: ") + hipGetErrorString((hipError_t)rc));
+}
+
+int qd_relay_batch_device(qd_graph* G, int32_t precision, int64_t B, const uint8_t* syn, int32_t syn_flags,
+                          const uint8_t* base, const uint8_t* readout, uint8_t* x_out, uint8_t* corr_out,
+                          void* llr_out, int32_t* iters, int32_t* legs, uint8_t* status, uint8_t* fail,
+                          int32_t only_failed, int32_t placement, void* stream) {
+    return guarded([&] {
+        RelayLayout L;
+        int kind = 0;
+        if (!check_relay_call(G, precision, B, syn, syn_flags, base, readout, fail, placement, &L, &kind)) return;
+        set_device(G);
+        const RelayArgs a{B, syn_flags, only_failed ? 1 : 0, syn, base, readout, x_out, corr_out, llr_out,
+                          iters, legs, status, fail, nullptr};
+        enqueue_relay(G, precision, a, L, kind, (hipStream_t)stream);
+    });
+}
+
+int qd_relay_batch(qd_graph* G, int32_t precision, int64_t B, const uint8_t* syn, int32_t syn_flags,
+                   const uint8_t* base, const uint8_t* readout, uint8_t* x_out, uint8_t* corr_out, void* llr_out,
+                   int32_t* iters, int32_t* legs, uint8_t* status, uint8_t* fail, int32_t only_failed,
+                   int32_t placement) {
+    return guarded([&] {
+        RelayLayout L;
+        int kind = 0;
+        if (!check_relay_call(G, precision, B, syn, syn_flags, base, readout, fail, placement, &L, &kind)) return;
+        set_device(G);
+        const DevGraph& g = G->dg;
+        const size_t tsz = precision == QD_F32 ? 4 : 8;
+        // workspace regions (256-B aligned): the inputs, then every output passed
+        struct Reg { size_t off, bytes; void* host; };
+        size_t off = 0;
+        auto reg = [&](size_t bytes, const void* h) {
+            Reg r{off, h ? bytes : 0, const_cast<void*>(h)};
+            if (h) off += (bytes + 255) / 256 * 256;
+            return r;
+        };
+        const Reg in[3] = {reg((size_t)B * g.m, syn), reg((size_t)B * g.n_data, base), reg((size_t)B * g.n_data, readout)};
+        const Reg outr[7] = {reg((size_t)B * g.n, x_out), reg((size_t)B * g.n_data, corr_out),
+                             reg((size_t)B * g.n * tsz, llr_out), reg((size_t)B * 4, iters), reg((size_t)B * 4, legs),
+                             reg((size_t)B, status), reg((size_t)B, fail)};
+        // no drain: every call of the host entry points ends in a stream synchronise
+        if (off > G->ws.cap) G->ws.regrow(off, off, "hipFree", "hipMalloc workspace", [] {});
+        auto* w = static_cast<uint8_t*>(G->ws.p);
+        auto dptr = [&](const Reg& r) -> void* { return r.bytes ? (void*)(w + r.off) : nullptr; };
+        hipStream_t s = G->stream;
+        for (const Reg& r : in)
+            if (r.bytes) hip_check(hipMemcpyAsync(dptr(r), r.host, r.bytes, hipMemcpyHostToDevice, s), "H2D relay input");
+        // only_failed: skipped shots keep what the caller's buffers hold, status is read
+        if (only_failed)
+            for (const Reg& r : outr)
+                if (r.bytes) hip_check(hipMemcpyAsync(dptr(r), r.host, r.bytes, hipMemcpyHostToDevice, s), "H2D relay output");
+        const RelayArgs a{B, syn_flags, only_failed ? 1 : 0, (const uint8_t*)dptr(in[0]), (const uint8_t*)dptr(in[1]),
+                          (const uint8_t*)dptr(in[2]), (uint8_t*)dptr(outr[0]), (uint8_t*)dptr(outr[1]), dptr(outr[2]),
+                          (int32_t*)dptr(outr[3]), (int32_t*)dptr(outr[4]), (uint8_t*)dptr(outr[5]),
+                          (uint8_t*)dptr(outr[6]), nullptr};
+        enqueue_relay(G, precision, a, L, kind, s);
+        for (const Reg& r : outr)
+            if (r.bytes) hip_check(hipMemcpyAsync(r.host, dptr(r), r.bytes, hipMemcpyDeviceToHost, s), "D2H relay output");
+        hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
     });
 }
 

@@ -12,6 +12,7 @@
 
 #include "qdec_circuit.h"
 #include "qdec_graph.h"
+#include "qdec_relay.h"
 
 namespace qdec {
 
@@ -195,6 +196,16 @@ inline const char* noted_name(const KernelEntry* e) { return e && e->noted ? e->
 // HIP call.  Read by qd_kernel_table_names.
 void append_wave_kernel_names(std::string& out);
 void append_block_kernel_names(std::string& out);
+
+// relay_block_kernel (qdec_relay.hip; arguments and layouts: qdec_relay.h).  Its
+// entries have a table of their own (relay_table: one per precision), outside
+// the decode plan's tables.  launch_relay enqueues `grid` workgroups; with the
+// messages in HBM `scratch` holds `grid` slots of L.slot_bytes, else it is null.
+void add_relay_kernels(KernelTable& t);
+const KernelTable& relay_table();
+void append_relay_kernel_names(std::string& out);
+int launch_relay(const DevGraph& g, int precision, const RelayArgs& a, const RelayTables& t, const RelayLayout& L,
+                 void* scratch, int64_t grid, hipStream_t stream);
 
 // ---------------------------------------------------------------- launch plan
 // Everything a decode decides before its first launch, decided once

@@ -1153,6 +1153,7 @@ void set_priors(HostGraph* G, const double* probs) {
         g.ms_allpos = 0;
         G->smp_thr = G->prior_arena->upload(thr);
         G->bp_priors = false;
+        G->prior_ms64.clear();
         return;
     }
     for (int j = 0; j < g.n; ++j) {
@@ -1206,6 +1207,7 @@ void set_priors(HostGraph* G, const double* probs) {
     }
     G->smp_thr = G->prior_arena->upload(thr);
     G->bp_priors = true;
+    G->prior_ms64.assign(ms64.begin(), ms64.begin() + g.n);
 }
 
 void table_digest(const HostGraph* G, uint64_t* digest, int64_t* bytes) {

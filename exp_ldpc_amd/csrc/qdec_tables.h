@@ -73,6 +73,9 @@ struct HostGraph {
     // set_priors: every probability lay inside (0, 1), so the BP priors exist;
     // false after a call with a 0 or a 1 among them (sampler thresholds only)
     bool bp_priors = false;
+    // the f64 min-sum priors log((1 - p) / p) of the last such call, kept on the
+    // host (empty otherwise): the relay stage's solution weights come from them
+    std::vector<double> prior_ms64;
     // fault sampler (sample_faults_kernel, qdec_sample.hip; kept beside DevGraph,
     // which every decode kernel takes by value): column j fires when a Philox
     // word is < smp_thr[j] (bern_threshold of the probability last given to

@@ -332,6 +332,95 @@ class Decoder:
         _abi.check(self._lib.qd_osd_hbm_info(self._handle, _abi.ptr(out)), "qd_osd_hbm_info")
         return int(out[0]), int(out[1]), int(out[2])
 
+    # ------------------------------------------------------------ relay-BP
+    def set_relay(self, gamma0: float = 0.125, pre_iter: int = 80, num_sets: int = 60, set_max_iter: int = 60,
+                  gamma_dist_interval=(-0.24, 0.66), stop_nconv: int = 1, alpha: float = 1.0,
+                  clip: float = 2.0 ** 64, seed: int = 0, gammas=None) -> np.ndarray:
+        """Tables of the relay stage (qd_graph_set_relay): leg 0
+        runs up to pre_iter min-sum iterations with memory strength gamma0,
+        legs 1 .. num_sets up to set_max_iter with row r - 1 of `gammas`
+        ([num_sets][n]; by default uniform on gamma_dist_interval from
+        numpy's PCG64(seed)).  Returns the table in use."""
+        num_sets = int(num_sets)
+        if gammas is None:
+            lo, hi = gamma_dist_interval
+            gammas = np.random.Generator(np.random.PCG64(seed)).uniform(lo, hi, (num_sets, self.n))
+        gammas = np.ascontiguousarray(np.asarray(gammas, dtype=np.float64).reshape(num_sets, self.n))
+        prm = _abi.QdRelayParams(float(gamma0), float(alpha), float(clip), int(pre_iter), num_sets,
+                                 int(set_max_iter), int(stop_nconv))
+        _abi.check(self._lib.qd_graph_set_relay(self._handle, C.byref(prm), _abi.ptr(gammas) if num_sets else None),
+                   "qd_graph_set_relay")
+        self.relay_params = dict(gamma0=float(gamma0), pre_iter=int(pre_iter), num_sets=num_sets,
+                                 set_max_iter=int(set_max_iter), stop_nconv=int(stop_nconv), alpha=float(alpha),
+                                 clip=float(clip))
+        self.relay_gammas = gammas
+        return gammas
+
+    def relay_device(self, B: int, *, syn=None, base=None, readout=None, x=None, corr=None, llr=None, iters=None,
+                     legs=None, status=None, fail=None, syn_flags: int = 0, only_failed: bool = False,
+                     placement: str = "auto", stream=None) -> None:
+        """Enqueue the relay stage (qd_relay_batch_device) for B device-resident
+        shots; with only_failed, `status` is read first and shots whose
+        BP-converged bit is set are left alone.  placement: "lds", "hbm" or
+        "auto" -- where a workgroup keeps its messages; the outputs do not
+        depend on it."""
+        if stream is None:
+            stream = _current_stream(self.device)
+        B = int(B)
+        llr_t = "float32" if self.precision == _abi.QD_F32 else "float64"
+        for name, t, dt, cols in (("syn", syn, "uint8", self.m), ("base", base, "uint8", self.n_data),
+                                  ("readout", readout, "uint8", self.n_data), ("x", x, "uint8", self.n),
+                                  ("corr", corr, "uint8", self.n_data), ("llr", llr, llr_t, self.n),
+                                  ("iters", iters, "int32", 1), ("legs", legs, "int32", 1),
+                                  ("status", status, "uint8", 1), ("fail", fail, "uint8", 1)):
+            self._check_device_buffer(name, t, dt, B * cols)
+        _abi.check(self._lib.qd_relay_batch_device(
+            self._handle, self.precision, B, _abi.ptr(syn), int(syn_flags), _abi.ptr(base), _abi.ptr(readout),
+            _abi.ptr(x), _abi.ptr(corr), _abi.ptr(llr), _abi.ptr(iters), _abi.ptr(legs), _abi.ptr(status),
+            _abi.ptr(fail), int(bool(only_failed)), relay_placement(placement), C.c_void_p(stream)),
+            "qd_relay_batch_device")
+
+    def relay(self, syn=None, *, base=None, readout=None, syn_flags: int = 0, status=None, placement: str = "auto",
+              want=("x", "corr", "iters", "legs", "status", "fail"), out=None) -> dict:
+        """The relay stage on host arrays (qd_relay_batch); returns numpy arrays
+        for `want` (any of x, corr, llr, iters, legs, status, fail).  With
+        `status` given (uint8 [B]) only the shots whose BP-converged bit is
+        clear are processed; the others keep what `out` (arrays by name) holds,
+        and their returned status is the one passed in."""
+        def u8(a, cols):
+            return None if a is None else np.ascontiguousarray(np.asarray(a), dtype=np.uint8).reshape(-1, cols)
+        syn, base, readout = u8(syn, self.m), u8(base, self.n_data), u8(readout, self.n_data)
+        B = next(a.shape[0] for a in (syn, base, readout) if a is not None)
+        shapes = {"x": ((B, self.n), np.uint8), "corr": ((B, self.n_data), np.uint8),
+                  "llr": ((B, self.n), self.llr_dtype), "iters": ((B,), np.int32), "legs": ((B,), np.int32),
+                  "status": ((B,), np.uint8), "fail": ((B,), np.uint8)}
+        only_failed = status is not None
+        res = {}
+        for name in want:
+            shape, dt = shapes[name]
+            given = None if out is None else out.get(name)
+            res[name] = (np.zeros(shape, dt) if given is None
+                         else np.ascontiguousarray(np.asarray(given), dtype=dt).reshape(shape).copy())
+        if only_failed:
+            res["status"] = np.ascontiguousarray(np.asarray(status), dtype=np.uint8).reshape(B).copy()
+        g = res.get
+        _abi.check(self._lib.qd_relay_batch(
+            self._handle, self.precision, B, _abi.ptr(syn), int(syn_flags), _abi.ptr(base), _abi.ptr(readout),
+            _abi.ptr(g("x")), _abi.ptr(g("corr")), _abi.ptr(g("llr")), _abi.ptr(g("iters")), _abi.ptr(g("legs")),
+            _abi.ptr(g("status")), _abi.ptr(g("fail")), int(only_failed), relay_placement(placement)),
+            "qd_relay_batch")
+        return res
+
+    def set_relay_slots(self, slots: int = 0) -> None:
+        """Workgroups of later relay launches in both placements
+        (qd_relay_set_slots); 0 = the default.  Results do not depend on it."""
+        _abi.check(self._lib.qd_relay_set_slots(self._handle, int(slots)), "qd_relay_set_slots")
+
+    def relay_info(self, placement: str = "auto") -> tuple[int, int, int, int]:
+        """(kind, dynamic LDS bytes, bytes per slot, workgroups of the last
+        launch) of qd_relay_info; kind 0 = messages in LDS, 1 = in HBM."""
+        return relay_info(self._handle, self.precision, placement)
+
     def set_wave_occupancy(self, waves_per_cu: int = 0) -> None:
         """Waves per CU of the wave BP kernels (qd_graph_set_wave_occupancy):
         0 = the default; more for decodes that run concurrently on several
@@ -445,6 +534,24 @@ def osd_rows_placement(rows) -> int:
     if rows not in OSD_ROWS:
         raise ValueError(f"rows must be one of {sorted(OSD_ROWS)}, got {rows!r}")
     return OSD_ROWS[rows]
+
+
+RELAY_PLACEMENTS = {"lds": _abi.QD_RELAY_LDS, "hbm": _abi.QD_RELAY_HBM, "auto": _abi.QD_RELAY_AUTO}
+
+
+def relay_placement(placement) -> int:
+    """placement ("lds" | "hbm" | "auto") -> QD_RELAY_*."""
+    if placement not in RELAY_PLACEMENTS:
+        raise ValueError(f"placement must be one of {sorted(RELAY_PLACEMENTS)}, got {placement!r}")
+    return RELAY_PLACEMENTS[placement]
+
+
+def relay_info(handle, precision: int, placement: str = "auto") -> tuple[int, int, int, int]:
+    """Decoder.relay_info for a raw qd_graph handle (a host-only graph included)."""
+    out = np.zeros(4, np.int64)
+    _abi.check(_abi.load().qd_relay_info(handle, int(precision), relay_placement(placement), _abi.ptr(out)),
+               "qd_relay_info")
+    return tuple(int(v) for v in out)
 
 
 def osd_kernel_info(handle, rows: str = "onchip"):

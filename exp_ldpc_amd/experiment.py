@@ -15,6 +15,9 @@ device.  Decoder modes (``--decoder_mode``):
   bposd_detector     bpd_detector followed by OSD on the same graph for the shots BP
                      leaves unconverged (under circuit noise nearly all of them);
                      the OSD rows live in device memory (csrc/qdec_osd_hbm.hip)
+  bprelay            bposd with relay-BP (csrc/qdec_relay.hip) on the BP-failed shots in
+                     place of OSD, at any R (build-defined)
+  bprelay_detector   bposd_detector with relay-BP in place of OSD
   bpd_detector       BP on the fault check matrix of a detector error model
                      (_experiment.py:128-151).  Under depolarizing_noise the
                      storage experiment's Z-sector DEM is written by
@@ -28,7 +31,11 @@ device.  Decoder modes (``--decoder_mode``):
 A detector error model of the user's own (any noise model, Stim's DEM text) is
 sampled on the device from its fault probabilities and decoded in batches by
 ``DemPipeline`` / ``run_dem_simulation`` (BP only by default, like
-``BPDetectorCorrect``; BP+OSD with ``osd=True``).
+``BPDetectorCorrect``; BP+OSD with ``osd=True``, BP+relay with ``relay={...}``).
+
+The relay stage's options travel in ``bp_osd_options`` under ``relay_*`` keys
+(add_relay_args / unpack_relay_args; Decoder.set_relay's arguments, plus
+``relay_placement``) or in the pipelines' ``relay`` argument.
 
 OSD runs on the GPU for the shots BP did not converge on (Decoder.osd_device),
 fused with the fold and the failure check: csrc/qdec_osd.hip with the rows on
@@ -62,11 +69,28 @@ from .spacetime import SpacetimeCode, SpacetimeCodeSingleShot
 from .storage_sim import build_storage_simulation
 
 __all__ = ["DECODER_MODES", "BatchPipeline", "DemPipeline", "run_dem_simulation","ShardError", "run_shards", "BPOSDCorrect", "BPOSDHybridCorrect", "BPOSDCorrectSingleShot",
-           "BPSSFCorrect", "BPDetectorCorrect", "run_simulation", "add_bposd_args", "unpack_bposd_args", "load_code", "p_sweep",
+           "BPSSFCorrect", "BPDetectorCorrect", "run_simulation", "add_bposd_args", "unpack_bposd_args",
+           "add_relay_args", "unpack_relay_args", "load_code", "p_sweep",
            "p_sweep_main", "parse_sweep_spec"]
 
 DECODER_MODES = ["bposd", "bposd_single_shot", "bposd_hybrid", "bpd_detector", "bposd_detector", "bpssf",
-                 "bpssf_hybrid", "bp"]
+                 "bpssf_hybrid", "bp", "bprelay", "bprelay_detector"]
+DETECTOR_MODES = ("bpd_detector", "bposd_detector", "bprelay_detector")
+# Decoder.set_relay's arguments, as relay_<name> keys of bp_osd_options
+RELAY_KEYS = ("gamma0", "pre_iter", "num_sets", "set_max_iter", "gamma_dist_interval", "stop_nconv", "alpha", "clip",
+              "seed", "gammas")
+
+
+def relay_options(bp_osd_options, relay=None):
+    """(Decoder.set_relay keyword arguments, placement) from the relay_* keys of
+    bp_osd_options, overridden by the `relay` dict of a pipeline."""
+    kw = {k[6:]: v for k, v in bp_osd_options.items() if k.startswith("relay_") and v is not None}
+    kw.update(relay or {})
+    placement = kw.pop("placement", "auto")
+    unknown = sorted(set(kw) - set(RELAY_KEYS))
+    if unknown:
+        raise ValueError(f"unknown relay options {unknown}")
+    return kw, placement
 # where the OSD stage of a pipeline runs: a device kernel with its rows on chip
 # (the host stage beyond 160 KiB), on chip or else in HBM, always in HBM, or the host stage
 OSD_ROWS = ("onchip", "auto", "hbm", "host")
@@ -132,11 +156,18 @@ class DemPipeline:
     F x) of the OSD solution.  osd_rows: "auto" (a device kernel, its rows on
     chip or in HBM), "onchip" (the host stage beyond 160 KiB), "hbm", "host".
     The [shots][faults] llr buffer is kept within llr_budget_bytes by decoding
-    in sub-batches; the flags do not depend on the split."""
+    in sub-batches; the flags do not depend on the split.
+
+    relay={...} (Decoder.set_relay's arguments, plus placement; {} for the
+    defaults), exclusive with osd=True: the shots BP leaves unconverged go
+    through relay-BP on the same graph instead, and their flag is any(obs ^ F x)
+    of its best solution (or of its last hard decision)."""
 
     def __init__(self, detector_error_model, bp_osd_options: Dict, *, device: int = 0, precision: str = "f64",
                  osd: bool = False, osd_rows: str = "auto", osd_threads: int = 0,
-                 llr_budget_bytes: int = DEFAULT_LLR_BUDGET):
+                 llr_budget_bytes: int = DEFAULT_LLR_BUDGET, relay: Dict | None = None):
+        if osd and relay is not None:
+            raise ValueError("osd=True and relay=... are exclusive")
         from .dem import DetectorSpacetimeCode
         self.dem = DetectorSpacetimeCode(detector_error_model)
         self.device = int(device)
@@ -157,6 +188,10 @@ class DemPipeline:
                            precision=precision, max_iter=int(o.get("max_iter", 0) or 0),
                            ms_scaling=float(o.get("ms_scaling_factor", 0.0)), logicals=fmap if self.k else None,
                            device=self.device)
+        self.relay = relay is not None
+        if self.relay:
+            kw, self.relay_placement = relay_options(o, relay)
+            self.dec.set_relay(**kw)
 
     def decoders(self):
         return [self.dec]
@@ -174,6 +209,8 @@ class DemPipeline:
         dev = torch.device("cuda", self.device)
         if self.osd:
             return self._run_osd(B, seed, stream_id, shot0, want_detail)
+        if self.relay:
+            packed = False  # the relay stage reads byte rows
         with torch.cuda.device(dev):
             det, faults, obs = sample_dem_device(self.dec, B, seed, stream_id, shot0, packed=packed,
                                                  want_obs=want_detail)
@@ -185,13 +222,21 @@ class DemPipeline:
                                        packed=packed)
             else:  # no observable: nothing can fail
                 self.dec.decode_device(B, syn=det, iters=iters, status=status, packed=packed)
+            bp_status = status.clone() if self.relay else status
+            if self.relay:
+                rd, fl = (faults, fail) if self.k else (None, None)
+                self.dec.relay_device(B, syn=det, readout=rd, status=status, fail=fl, only_failed=True,
+                                      placement=self.relay_placement)
             detail = None
             if want_detail:
                 det_h = det.cpu().numpy()
                 detail = {"det": unpack_rows(det_h.view(np.uint64), self.dec.m) if packed else det_h,
                           "obs": obs.cpu().numpy() if obs is not None else np.zeros((B, 0), np.uint8),
-                          "iters": iters.cpu().numpy(), "status": status.cpu().numpy()}
-            return BatchResult(fail=fail.cpu().numpy().astype(bool), bp_converged=int((status & 1).sum().item()),
+                          "iters": iters.cpu().numpy(), "status": bp_status.cpu().numpy()}
+                if self.relay:
+                    detail["faults"] = faults.cpu().numpy()
+                    detail["relay_status"] = status.cpu().numpy()
+            return BatchResult(fail=fail.cpu().numpy().astype(bool), bp_converged=int((bp_status & 1).sum().item()),
                                iters_sum=int(iters.to(torch.int64).sum().item()), ssf_steps_sum=0, detail=detail)
 
 
@@ -246,15 +291,15 @@ class DemPipeline:
 def run_dem_simulation(samples, detector_error_model, bp_osd_options, *, seed: int, stream_id: int = 0,
                        shot0: int = 0, device: int = 0, batch: int = 1 << 18, precision: str = "f64",
                        stats: dict | None = None, osd: bool = False, osd_rows: str = "auto",
-                       llr_budget_bytes: int = DEFAULT_LLR_BUDGET):
+                       llr_budget_bytes: int = DEFAULT_LLR_BUDGET, relay: Dict | None = None):
     """Sample and decode `samples` shots of a detector error model (DEM text or a
     parsed model) on one GPU; returns a bool ndarray of logical-failure flags,
     shaped like run_simulation's.  Replaces the reference's per-shot loop over
     Stim's detector samples and BPDetectorCorrect (_experiment.py:186-209) for a
     user-supplied DEM; the flags do not depend on `batch`.  osd=True: BP+OSD
-    (DemPipeline's osd, osd_rows, llr_budget_bytes)."""
+    (DemPipeline's osd, osd_rows, llr_budget_bytes); relay={...}: BP+relay."""
     pipe = DemPipeline(detector_error_model, bp_osd_options, device=device, precision=precision, osd=osd,
-                       osd_rows=osd_rows, llr_budget_bytes=llr_budget_bytes)
+                       osd_rows=osd_rows, llr_budget_bytes=llr_budget_bytes, relay=relay)
     out = np.zeros(samples, dtype=bool)
     agg = {"bp_converged": 0, "iters_sum": 0, "ssf_steps_sum": 0}
     for start in range(0, samples, batch):
@@ -276,13 +321,16 @@ class BatchPipeline:
     def __init__(self, code, rounds: int, mode: str, bp_osd_options: Dict, priors: Tuple[float, float], *,
                  device: int = 0, precision: str = "f64", use_x_logicals: bool = False, osd_threads: int = 0,
                  noise=None, dem_source: str | None = None, sim=None, osd_rows: str | None = None,
-                 llr_budget_bytes: int = DEFAULT_LLR_BUDGET, approximate_disjoint_errors: bool = False):
+                 llr_budget_bytes: int = DEFAULT_LLR_BUDGET, approximate_disjoint_errors: bool = False,
+                 relay: Dict | None = None):
         if mode not in DECODER_MODES:
             raise RuntimeError("Unknown decoder operation mode")
         if dem_source not in (None, "circuit"):
             raise ValueError('dem_source is None (by noise model) or "circuit"')
-        if dem_source is not None and mode not in ("bpd_detector", "bposd_detector"):
-            raise ValueError("dem_source applies to bpd_detector and bposd_detector only")
+        if dem_source is not None and mode not in DETECTOR_MODES:
+            raise ValueError("dem_source applies to bpd_detector, bposd_detector and bprelay_detector only")
+        if relay is not None and mode not in ("bprelay", "bprelay_detector"):
+            raise ValueError("relay applies to bprelay and bprelay_detector only")
         # None: the existing modes keep their selection (on chip, else the host
         # stage); the DEM mode's graphs are past the LDS limit, so it takes HBM
         self.osd_rows = _check_osd_rows(osd_rows, "auto" if mode == "bposd_detector" else "onchip")
@@ -314,7 +362,9 @@ class BatchPipeline:
         R, n = self.R, self.n
         lz = self.L if self.L.shape[0] else None
         # spacetime stage (modes that use it)
-        if mode in ("bposd", "bposd_hybrid", "bpssf_hybrid", "bp"):
+        if mode in ("bprelay", "bprelay_detector"):
+            self.relay_kw, self.relay_placement = relay_options(o, relay)
+        if mode in ("bposd", "bposd_hybrid", "bpssf_hybrid", "bp", "bprelay"):
             st = SpacetimeCode(self.H, R)
             Hst = st.spacetime_check_matrix
             prior = np.empty(Hst.shape[1])
@@ -322,6 +372,8 @@ class BatchPipeline:
             prior[(R + 1) * n:] = meas_prior
             self.st = Decoder(Hst, prior, n_data=n, fold_blocks=R + 1, logicals=lz, **common)
             self.st_osd = OsdSolver(Hst, osd_method, osd_order, osd_threads) if mode == "bposd" else None
+            if mode == "bprelay":
+                self.st.set_relay(**self.relay_kw)
         # final-round stage on H
         if mode in ("bposd_hybrid", "bposd_single_shot"):
             self.fin = Decoder(self.H, data_prior, logicals=lz, **common)
@@ -336,7 +388,7 @@ class BatchPipeline:
             prior[n:] = meas_prior
             self.ss = Decoder(Hss, prior, n_data=n, fold_blocks=1, **common)
             self.ss_osd = OsdSolver(Hss, osd_method, osd_order, osd_threads)
-        if mode in ("bpd_detector", "bposd_detector"):
+        if mode in DETECTOR_MODES:
             # reference BPDetectorCorrect (_experiment.py:128-151): BP (no OSD) on the
             # DEM's fault check matrix with its fault priors.  The sampler's
             # spacetime syndrome is the DEM's detector vector; the readout-flip
@@ -354,6 +406,8 @@ class BatchPipeline:
             # unconverged (under circuit noise nearly all of them)
             self.det_osd = (OsdSolver(self.dem.fault_check_matrix, osd_method, osd_order, osd_threads)
                             if mode == "bposd_detector" else None)
+            if mode == "bprelay_detector":
+                self.det.set_relay(**self.relay_kw)
         # a plain-H decoder for the sampler
         self.sampler_graph = Decoder(self.H, 0.01, device=self.device)
 
@@ -506,6 +560,28 @@ class BatchPipeline:
             fixes.append((lo + bad.cpu().numpy(), flags))
         return fixes
 
+    def _run_bprelay_detector(self, syn, readout, iters, status, fail):
+        """BP on the DEM graph, then relay-BP on the same graph for the shots it
+        leaves unconverged; the flag is any(obs ^ F x) with x the relay stage's
+        best solution (its last hard decision when it found none), fused in
+        the relay kernel's failure check.  No llr buffer, so no sub-batches.
+        Returns the BP stage's converged count (a device scalar)."""
+        B, nf, n = syn.shape[0], self.n_faults, self.n
+        torch = _torch()
+        v = fl = None
+        if self.L.shape[0] > 0:
+            fl = fail
+            if self.dem_source == "circuit":
+                v = self._circuit_readout_faults(readout, 0, B)
+            else:
+                v = torch.zeros((B, nf), dtype=torch.uint8, device=syn.device)
+                v[:, nf - n:] = readout
+        self.det.decode_device(B, syn=syn, readout=v, iters=iters, status=status, fail=fl)
+        conv = (status & 1).sum()
+        self.det.relay_device(B, syn=syn, readout=v, status=status, fail=fl, only_failed=True,
+                              placement=self.relay_placement)
+        return conv
+
     def run(self, syn, readout, want_corrections: bool = False) -> BatchResult:
         torch = _torch()
         B = syn.shape[0]
@@ -520,6 +596,7 @@ class BatchPipeline:
         corr = torch.zeros((B, n), **u8)
         host_fix = None  # (idx, corrections) applied on host
         fail_fix = []    # (idx, flags) of shots whose OSD ran on the host without a correction to fold
+        bp_conv = None   # the BP stage's converged count, where a later stage rewrites status
         mode = self.mode
         if mode in ("bp", "bposd"):
             need_llr = mode == "bposd"
@@ -563,6 +640,13 @@ class BatchPipeline:
         elif mode == "bpssf":
             self.fin.decode_device(B, syn=syn, readout=readout, corr=corr, iters=iters, status=status,
                                    ssf_steps=steps, fail=fail)
+        elif mode == "bprelay":
+            self.st.decode_device(B, syn=syn, readout=readout, corr=corr, iters=iters, status=status, fail=fail)
+            bp_conv = (status & 1).sum()  # the relay stage rewrites the status of the shots it takes
+            self.st.relay_device(B, syn=syn, readout=readout, corr=corr, status=status, fail=fail, only_failed=True,
+                                 placement=self.relay_placement)
+        elif mode == "bprelay_detector":
+            bp_conv = self._run_bprelay_detector(syn, readout, iters, status, fail)
         elif mode == "bposd_detector":
             fail_fix = self._run_bposd_detector(syn, readout, iters, status, fail)
         elif mode == "bpd_detector" and self.dem_source == "circuit":
@@ -624,7 +708,7 @@ class BatchPipeline:
             fail_h[idx] = self._fail_host(readout.index_select(0, torch.from_numpy(idx).to(dev)).cpu().numpy(), c)
         for idx, flags in fail_fix:
             fail_h[idx] = flags
-        return BatchResult(fail=fail_h, bp_converged=int((status & 1).sum().item()),
+        return BatchResult(fail=fail_h, bp_converged=int(((status & 1).sum() if bp_conv is None else bp_conv).item()),
                            iters_sum=int(iters.to(torch.int64).sum().item()),
                            ssf_steps_sum=int(steps.to(torch.int64).sum().item()),
                            corrections=corr_h if want_corrections else None)
@@ -753,6 +837,32 @@ def add_bposd_args(parser):
                         help="Min sum scaling factor. Use variable scaling factor method if 0", default=0)
     parser.add_argument("--bposd_osd_method", choices=["osd_e", "osd_cs", "osd0"], help="OSD method", default="osd_cs")
     parser.add_argument("--bposd_osd_order", type=int, help="OSD search depth", default=7)
+
+
+def add_relay_args(parser):
+    """Relay-BP options of bprelay / bprelay_detector (Decoder.set_relay's
+    defaults); no reference counterpart."""
+    def interval(x):
+        lo, hi = (float(v) for v in x.strip("() ").split(","))
+        return lo, hi
+    parser.add_argument("--relay_gamma0", type=float, default=0.125, help="memory strength of the first leg")
+    parser.add_argument("--relay_pre_iter", type=int, default=80, help="iterations of the first leg")
+    parser.add_argument("--relay_num_sets", type=int, default=60, help="further legs, each with its own strengths")
+    parser.add_argument("--relay_set_max_iter", type=int, default=60, help="iterations of each further leg")
+    parser.add_argument("--relay_gamma_dist_interval", type=interval, default=(-0.24, 0.66),
+                        help="(lo, hi): the further legs' strengths are uniform on it")
+    parser.add_argument("--relay_stop_nconv", type=int, default=1, help="stop after this many converged legs")
+    parser.add_argument("--relay_alpha", type=float, default=1.0, help="min-sum scaling factor of the relay legs")
+    parser.add_argument("--relay_seed", type=int, default=0, help="seed of the strengths (numpy PCG64)")
+    parser.add_argument("--relay_placement", choices=["auto", "lds", "hbm"], default="auto",
+                        help="where a workgroup keeps its messages")
+
+
+def unpack_relay_args(parsed_args):
+    """The relay_* keys of bp_osd_options from add_relay_args' arguments."""
+    names = ("gamma0", "pre_iter", "num_sets", "set_max_iter", "gamma_dist_interval", "stop_nconv", "alpha", "seed",
+             "placement")
+    return {f"relay_{k}": getattr(parsed_args, f"relay_{k}") for k in names}
 
 
 def unpack_bposd_args(parsed_args, code):
@@ -1030,7 +1140,7 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
         point["config_fp"] = fp
         if pipes[0].dem_source == "circuit":
             point["dem_sector"] = "circuit"          # dem.detector_error_model of the sampled circuit
-        elif mode in ("bpd_detector", "bposd_detector") and rounds >= 2:
+        elif mode in DETECTOR_MODES and rounds >= 2:
             point["dem_sector"] = "z_only_unpinned"  # see BatchPipeline's warning / dem.storage_experiment_dem
         data.append(point)
         if checkpoint:
@@ -1071,6 +1181,7 @@ def p_sweep_main(noise_model_args, noise_model, meas_prior, data_prior):
                         help="Perform the sweep with linearly spaced points. The default is uniform spacing in log "
                              "space")
     add_bposd_args(parser)
+    add_relay_args(parser)
     parser.add_argument("--gpus", type=int, default=None, help="GPUs to shard shots over (default: all visible)")
     parser.add_argument("--devices", type=lambda v: [int(x) for x in v.split(",") if x.strip()], default=None,
                         help="comma-separated device ordinals, one shot shard each (repeats allowed; overrides --gpus)")
@@ -1090,6 +1201,8 @@ def p_sweep_main(noise_model_args, noise_model, meas_prior, data_prior):
     args = parser.parse_args(sys.argv[1:])
     code = load_code(args)
     bp_osd_options = unpack_bposd_args(args, code)
+    if args.decoder_mode in ("bprelay", "bprelay_detector"):
+        bp_osd_options.update(unpack_relay_args(args))
     sweep =np.linspace(*args.p_sweep) if args.linspace else np.geomspace(*args.p_sweep)
     result = p_sweep(samples=args.samples, code=code, rounds=args.rounds, noise_model=noise_model,
                      noise_model_args=noise_model_args, meas_prior=meas_prior, data_prior=data_prior,

@@ -18,6 +18,9 @@ int ndarray of length n; afterwards ``.converge``, ``.iter``,
 ``.osdw_decoding``) are set as in ldpc.  ``decode_batch`` is the throughput
 path.  Extra: ``precision`` ('f64' = ldpc's double arithmetic, the default here;
 'f32'), ``device``.
+
+``relay_decoder`` has no ldpc counterpart: relay-BP (Decoder.set_relay /
+Decoder.relay) behind the same object interface.
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ import scipy.sparse as sp
 from .decoder import Decoder, as_csr01, parse_bp_method
 from . import _abi
 
-__all__ = ["bp_decoder", "bposd_decoder"]
+__all__ = ["bp_decoder", "bposd_decoder", "relay_decoder"]
 
 
 def _resolve_probs(n, kwargs):
@@ -146,3 +149,44 @@ class bposd_decoder(bp_decoder):
         self.osd0_decoding = out["osd0"][0].copy()
         self.osdw_decoding = out["osdw"][0].copy()
         return self.osdw_decoding.astype(np.int64)
+
+
+class relay_decoder(bp_decoder):
+    """Relay-BP in the style of ``bp_decoder``: an ensemble of min-sum legs with
+    per-variable memory strengths, each starting from the previous leg's
+    marginals; ``.decode`` returns the lowest-weight solution found (the last
+    hard decision when none was).  Keywords besides the channel: Decoder.
+    set_relay's (gamma0, pre_iter, num_sets, set_max_iter, gamma_dist_interval,
+    stop_nconv, clip, seed, gammas), ``ms_scaling_factor`` (the fixed alpha,
+    default 1.0), ``placement``, ``precision``, ``device``.  After ``.decode``:
+    ``.converge`` (a solution was found), ``.iter`` (all iterations run),
+    ``.legs`` (legs run), ``.log_prob_ratios`` (the last marginals)."""
+
+    RELAY_KEYS = ("gamma0", "pre_iter", "num_sets", "set_max_iter", "gamma_dist_interval", "stop_nconv", "clip",
+                  "seed", "gammas")
+
+    def __init__(self, parity_check_matrix, **kwargs):
+        kw = dict(kwargs)
+        kw.setdefault("bp_method", "ms")
+        kw.setdefault("max_iter", int(kwargs.get("pre_iter", 80)))
+        super().__init__(parity_check_matrix, **kw)
+        if self.ms_scaling_factor <= 0:
+            raise ValueError("relay_decoder needs a fixed ms_scaling_factor > 0")
+        self.placement = kwargs.get("placement", "auto")
+        self._relay_kw = {k: kwargs[k] for k in self.RELAY_KEYS if k in kwargs}
+        self.gammas = self._dec.set_relay(alpha=self.ms_scaling_factor, **self._relay_kw)
+        self.legs = 0
+
+    def decode_batch(self, vectors) -> dict:
+        """B shots at once; returns {'x', 'llr', 'iters', 'legs', 'status'}."""
+        syn, _ = self._as_syndromes(vectors)
+        return self._dec.relay(syn, placement=self.placement, want=("x", "llr", "iters", "legs", "status"))
+
+    def decode(self, input_vector) -> np.ndarray:
+        out = self.decode_batch(input_vector)
+        self.bp_decoding = out["x"][0].copy()
+        self.log_prob_ratios = out["llr"][0].astype(np.float64)
+        self.iter = int(out["iters"][0])
+        self.legs = int(out["legs"][0])
+        self.converge = int(out["status"][0] & _abi.QD_ST_BP_CONVERGED)
+        return self.bp_decoding.astype(np.int64)

@@ -431,6 +431,90 @@ int qd_osd_set_slots(qd_graph* g, int64_t slots);
  * slots of the last HBM launch, out[2] = scratch bytes held. */
 int qd_osd_hbm_info(const qd_graph* g, int64_t out[3]);
 
+/* Relay-BP: a post-processor made of message passing alone, for the shots plain
+ * BP leaves open on graphs without flip sets (circuit detector error models),
+ * where OSD's elimination is the slow stage.  An ensemble of min-sum "legs"
+ * with per-variable memory strengths gamma_j: each leg starts from the previous
+ * leg's marginals, and the lowest-weight solution found is kept.  No reference
+ * counterpart (the reference has no decoder of its own): the algorithm is
+ * build-defined, fixed to the last rounding in DESIGN 3.6d, with
+ * tests/relay_model.py as its model.  All arithmetic in T = float or double,
+ * no contraction.
+ *
+ * qd_graph_set_relay: the stage's tables.  Leg 0 runs up to pre_iter iterations
+ * with gamma_j = gamma0, leg r = 1 .. num_sets up to set_max_iter with row r - 1
+ * of gammas [num_sets][n] (doubles, rounded once to T; NULL with num_sets = 0);
+ * alpha is the fixed min-sum scaling factor, clip (2^64 by default in the Python
+ * binding) the bound of marginals and messages, stop_nconv the number of
+ * converged legs after which a shot stops.  Solution weights are llrint(prior
+ * 2^16) of the f64 min-sum priors.  Works on host-only graphs; the tables are
+ * rebuilt by every later qd_graph_set_priors.  Errors: -52 a parameter out of
+ * range (alpha not finite or <= 0, clip not > 0 (+inf: no clamp), gamma0 or a
+ * gamma not finite, pre_iter, set_max_iter, stop_nconv < 1, num_sets < 0, gammas
+ * NULL with num_sets > 0; qd_relay_set_slots: slots outside 0 .. 2^20), -53 (num_sets + 1) n above 2^23 table entries, -5
+ * priors never set, -51 priors holding a 0 or a 1.
+ *
+ * qd_relay_batch_device: B shots on device buffers, enqueued on `stream`.
+ * Inputs as qd_decode_batch_device's byte rows (syn_flags: QD_SYN_ADD_BASE /
+ * _READOUT; QD_INPUT_PACKED is refused).  Outputs (each nullable):
+ *   x_out    uint8 [B][n]      the best solution, or the last hard decision
+ *   corr_out uint8 [B][n_data] base ^ fold(x_out)
+ *   llr_out  [B][n] float / double: the marginals after the last iteration run
+ *   iters    int32 [B]         all iterations run
+ *   legs     int32 [B]         legs run
+ *   status   uint8 [B]         3 (QD_ST_BP_CONVERGED | QD_ST_SATISFIED) when a
+ *                              solution was found, else 0
+ *   fail     uint8 [B]         any(Lz (readout ^ corr_out)) (logicals + readout)
+ * With only_failed != 0, status is read first: a shot whose QD_ST_BP_CONVERGED
+ * bit is set is skipped and none of its outputs is touched.  placement: where a
+ * workgroup keeps v2c, c2v and the marginals --
+ *   QD_RELAY_LDS   dynamic LDS with the shot state (-56 above 160 KiB)
+ *   QD_RELAY_HBM   a slot of a scratch the handle owns; bytes and bits stay in
+ *                  LDS (-56 when that part alone exceeds 160 KiB)
+ *   QD_RELAY_AUTO  LDS where it fits, else HBM
+ * Both give the same bits.  The scratch follows the OSD scratch's policy: grown
+ * on demand within a quarter of the free device memory (-59 when that holds no
+ * slot), halved on a refusal down to one slot (-58).  Launches on one handle
+ * from different streams are chained through an event.  Errors: -4 precision,
+ * -8 B < 0, -55 placement, -57 inputs the stage does not take (packed rows,
+ * unknown syn_flags, a failure check over more than 256 logicals), -54
+ * qd_graph_set_relay not called, -5 / -51 priors, -7 no syndrome source, -56,
+ * -16 host-only graph.  B = 0 returns 0 and writes nothing.
+ * qd_relay_batch: the same on host buffers, synchronous.
+ * qd_relay_set_slots: workgroups of later launches in both placements (0 = the
+ * default: 2 per compute unit in HBM, what fits in LDS); a launch uses at most
+ * B.  Results do not depend on it.
+ * qd_relay_info: out[4] = kind (QD_RELAY_LDS or QD_RELAY_HBM) the placement
+ * launches, its dynamic LDS bytes, bytes per slot (0 for LDS), workgroups of
+ * the last launch.  No HIP call; host-only graphs answer.  -56 when the
+ * placement has no kernel for the graph.
+ * qd_relay_kernel_names: as qd_kernel_table_names for the relay kernels' own
+ * table (which that list does not include). */
+#define QD_RELAY_LDS 0
+#define QD_RELAY_HBM 1
+#define QD_RELAY_AUTO 2
+typedef struct qd_relay_params {
+    double gamma0;
+    double alpha;
+    double clip;
+    int32_t pre_iter;
+    int32_t num_sets;
+    int32_t set_max_iter;
+    int32_t stop_nconv;
+} qd_relay_params;
+int qd_graph_set_relay(qd_graph* g, const qd_relay_params* prm, const double* gammas);
+int qd_relay_batch_device(qd_graph* g, int32_t precision, int64_t B, const uint8_t* syn, int32_t syn_flags,
+                          const uint8_t* base, const uint8_t* readout, uint8_t* x_out, uint8_t* corr_out,
+                          void* llr_out, int32_t* iters, int32_t* legs, uint8_t* status, uint8_t* fail,
+                          int32_t only_failed, int32_t placement, void* stream);
+int qd_relay_batch(qd_graph* g, int32_t precision, int64_t B, const uint8_t* syn, int32_t syn_flags,
+                   const uint8_t* base, const uint8_t* readout, uint8_t* x_out, uint8_t* corr_out, void* llr_out,
+                   int32_t* iters, int32_t* legs, uint8_t* status, uint8_t* fail, int32_t only_failed,
+                   int32_t placement);
+int qd_relay_set_slots(qd_graph* g, int64_t slots);
+int qd_relay_info(const qd_graph* g, int32_t precision, int32_t placement, int64_t out[4]);
+int64_t qd_relay_kernel_names(char* buf, int64_t cap);
+
 /* Kernel timing for measurement: with capacity > 0, the next `capacity` decode
  * calls record HIP events on their launch stream immediately before the BP kernel,
  * after it and after the SSF kernel.  qd_graph_read_timing returns the per-call
