@@ -220,11 +220,15 @@ void note_kernels(qd_graph* G) {
     G->last_pre = n.pre ? n.pre : "";
 }
 
-void put_name(const std::string& v, char* out, int32_t len) {
-    if (!out || len <= 0) return;
-    const size_t k = std::min(v.size(), (size_t)len - 1);
-    std::memcpy(out, v.data(), k);
-    out[k] = '\0';
+// the one copy of a string into a caller's buffer: cut to len - 1 characters
+// and terminated; returns the whole length
+int64_t put_name(const std::string& v, char* out, int64_t len) {
+    if (out && len > 0) {
+        const size_t k = std::min(v.size(), (size_t)len - 1);
+        std::memcpy(out, v.data(), k);
+        out[k] = '\0';
+    }
+    return (int64_t)v.size();
 }
 
 // a stage whose instantiation the library does not build fails here, before anything is enqueued
@@ -483,13 +487,7 @@ int64_t qd_graph_hgp_source(qd_graph* G, char* buf, int64_t cap) {
         check_graph(G);
         HgpPlan* P = hgp_plan_of(G);
         if (!P) throw Fail(-90, "not a hypergraph-product check matrix");
-        const std::string& s = hgp_plan_source(P);
-        len = (int64_t)s.size();
-        if (buf && cap > 0) {
-            const size_t k = std::min<size_t>(s.size(), (size_t)cap - 1);
-            std::memcpy(buf, s.data(), k);
-            buf[k] = 0;
-        }
+        len = put_name(hgp_plan_source(P), buf, cap);
     });
     return e ? e : len;
 }
@@ -653,48 +651,25 @@ int qd_decode_batch(qd_graph* G, const qd_params* p, int64_t B, const uint8_t* s
         const bool pk = (p->syn_flags & QD_INPUT_PACKED) != 0;
         const size_t syn_row = pk ? ((size_t)g.m + 63) / 64 * 8 : (size_t)g.m;
         const size_t dat_row = pk ? ((size_t)g.n_data + 63) / 64 * 8 : (size_t)g.n_data;
-        // workspace layout (each region 256-B aligned)
-        struct Reg { size_t off, bytes; };
-        size_t off = 0;
-        auto reg = [&](size_t bytes, bool on) {
-            Reg r{off, on ? bytes : 0};
-            if (on) off += (bytes + 255) / 256 * 256;
-            return r;
-        };
-        const Reg r_syn = reg((size_t)B * syn_row, syn != nullptr);
-        const Reg r_base = reg((size_t)B * dat_row, base != nullptr);
-        const Reg r_rd = reg((size_t)B * dat_row, readout != nullptr);
-        const Reg r_x = reg((size_t)B * g.n, x_out != nullptr);
-        const Reg r_corr = reg((size_t)B * g.n_data, corr_out != nullptr);
-        const Reg r_llr = reg((size_t)B * g.n * tsz, llr_out != nullptr);
-        const Reg r_it = reg((size_t)B * 4, iters != nullptr);
-        const Reg r_st = reg((size_t)B, status != nullptr);
-        const Reg r_ss = reg((size_t)B * 4, ssf_steps != nullptr);
-        const Reg r_fl = reg((size_t)B, fail != nullptr);
-        // no drain: every call of this entry point ends in a stream synchronise,
-        // so the workspace has no user left
-        if (off > G->ws.cap) G->ws.regrow(off, off, "hipFree", "hipMalloc workspace", [] {});
-        auto* w = static_cast<uint8_t*>(G->ws.p);
-        auto dptr = [&](const Reg& r) -> void* { return r.bytes ? (void*)(w + r.off) : nullptr; };
+        HostStage st;  // regions 0-2 the inputs, 3-9 the outputs
+        st.add(syn, (size_t)B * syn_row, "syn");
+        st.add(base, (size_t)B * dat_row, "base");
+        st.add(readout, (size_t)B * dat_row, "readout");
+        st.add(x_out, (size_t)B * g.n, "x");
+        st.add(corr_out, (size_t)B * g.n_data, "corr");
+        st.add(llr_out, (size_t)B * g.n * tsz, "llr");
+        st.add(iters, (size_t)B * 4, "iters");
+        st.add(status, (size_t)B, "status");
+        st.add(ssf_steps, (size_t)B * 4, "ssf_steps");
+        st.add(fail, (size_t)B, "fail");
+        st.place(G->ws);
         hipStream_t s = G->stream;
-        if (syn) hip_check(hipMemcpyAsync(dptr(r_syn), syn, r_syn.bytes, hipMemcpyHostToDevice, s), "H2D syn");
-        if (base) hip_check(hipMemcpyAsync(dptr(r_base), base, r_base.bytes, hipMemcpyHostToDevice, s), "H2D base");
-        if (readout) hip_check(hipMemcpyAsync(dptr(r_rd), readout, r_rd.bytes, hipMemcpyHostToDevice, s), "H2D readout");
-        DecodeArgs a = make_args(G, p, B, (const uint8_t*)dptr(r_syn), (const uint8_t*)dptr(r_base),
-                                 (const uint8_t*)dptr(r_rd), (uint8_t*)dptr(r_x), (uint8_t*)dptr(r_corr), dptr(r_llr),
-                                 (int32_t*)dptr(r_it), (uint8_t*)dptr(r_st), (int32_t*)dptr(r_ss), (uint8_t*)dptr(r_fl));
-        enqueue_decode(G, p, a, s, false);  // SSF stays on s: the copies below follow it
-        auto d2h = [&](void* h, const Reg& r, const char* what) {
-            if (h) hip_check(hipMemcpyAsync(h, dptr(r), r.bytes, hipMemcpyDeviceToHost, s), what);
-        };
-        d2h(x_out, r_x, "D2H x");
-        d2h(corr_out, r_corr, "D2H corr");
-        d2h(llr_out, r_llr, "D2H llr");
-        d2h(iters, r_it, "D2H iters");
-        d2h(status, r_st, "D2H status");
-        d2h(ssf_steps, r_ss, "D2H ssf_steps");
-        d2h(fail, r_fl, "D2H fail");
-        hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        st.copy(0, 3, true, s);
+        DecodeArgs a = make_args(G, p, B, st.dev<uint8_t>(0), st.dev<uint8_t>(1), st.dev<uint8_t>(2), st.dev<uint8_t>(3),
+                                 st.dev<uint8_t>(4), st.dev(5), st.dev<int32_t>(6), st.dev<uint8_t>(7),
+                                 st.dev<int32_t>(8), st.dev<uint8_t>(9));
+        enqueue_decode(G, p, a, s, false);  // SSF stays on s: the copies out follow it
+        st.finish(3, s);
     });
 }
 
@@ -919,12 +894,7 @@ int64_t qd_relay_kernel_names(char* buf, int64_t cap) {
     const int e = guarded([&] {
         std::string s;
         append_relay_kernel_names(s);
-        len = (int64_t)s.size();
-        if (buf && cap > 0) {
-            const size_t k = std::min<size_t>(s.size(), (size_t)cap - 1);
-            std::memcpy(buf, s.data(), k);
-            buf[k] = 0;
-        }
+        len = put_name(s, buf, cap);
     });
     return e ? e : len;
 }
@@ -1001,37 +971,26 @@ int qd_relay_batch(qd_graph* G, int32_t precision, int64_t B, const uint8_t* syn
         set_device(G);
         const DevGraph& g = G->dg;
         const size_t tsz = precision == QD_F32 ? 4 : 8;
-        // workspace regions (256-B aligned): the inputs, then every output passed
-        struct Reg { size_t off, bytes; void* host; };
-        size_t off = 0;
-        auto reg = [&](size_t bytes, const void* h) {
-            Reg r{off, h ? bytes : 0, const_cast<void*>(h)};
-            if (h) off += (bytes + 255) / 256 * 256;
-            return r;
-        };
-        const Reg in[3] = {reg((size_t)B * g.m, syn), reg((size_t)B * g.n_data, base), reg((size_t)B * g.n_data, readout)};
-        const Reg outr[7] = {reg((size_t)B * g.n, x_out), reg((size_t)B * g.n_data, corr_out),
-                             reg((size_t)B * g.n * tsz, llr_out), reg((size_t)B * 4, iters), reg((size_t)B * 4, legs),
-                             reg((size_t)B, status), reg((size_t)B, fail)};
-        // no drain: every call of the host entry points ends in a stream synchronise
-        if (off > G->ws.cap) G->ws.regrow(off, off, "hipFree", "hipMalloc workspace", [] {});
-        auto* w = static_cast<uint8_t*>(G->ws.p);
-        auto dptr = [&](const Reg& r) -> void* { return r.bytes ? (void*)(w + r.off) : nullptr; };
+        HostStage st;  // regions 0-2 the inputs, 3-9 every output passed
+        st.add(syn, (size_t)B * g.m, "relay input");
+        st.add(base, (size_t)B * g.n_data, "relay input");
+        st.add(readout, (size_t)B * g.n_data, "relay input");
+        st.add(x_out, (size_t)B * g.n, "relay output");
+        st.add(corr_out, (size_t)B * g.n_data, "relay output");
+        st.add(llr_out, (size_t)B * g.n * tsz, "relay output");
+        st.add(iters, (size_t)B * 4, "relay output");
+        st.add(legs, (size_t)B * 4, "relay output");
+        st.add(status, (size_t)B, "relay output");
+        st.add(fail, (size_t)B, "relay output");
+        st.place(G->ws);
         hipStream_t s = G->stream;
-        for (const Reg& r : in)
-            if (r.bytes) hip_check(hipMemcpyAsync(dptr(r), r.host, r.bytes, hipMemcpyHostToDevice, s), "H2D relay input");
         // only_failed: skipped shots keep what the caller's buffers hold, status is read
-        if (only_failed)
-            for (const Reg& r : outr)
-                if (r.bytes) hip_check(hipMemcpyAsync(dptr(r), r.host, r.bytes, hipMemcpyHostToDevice, s), "H2D relay output");
-        const RelayArgs a{B, syn_flags, only_failed ? 1 : 0, (const uint8_t*)dptr(in[0]), (const uint8_t*)dptr(in[1]),
-                          (const uint8_t*)dptr(in[2]), (uint8_t*)dptr(outr[0]), (uint8_t*)dptr(outr[1]), dptr(outr[2]),
-                          (int32_t*)dptr(outr[3]), (int32_t*)dptr(outr[4]), (uint8_t*)dptr(outr[5]),
-                          (uint8_t*)dptr(outr[6]), nullptr};
+        st.copy(0, only_failed ? 10 : 3, true, s);
+        const RelayArgs a{B, syn_flags, only_failed ? 1 : 0, st.dev<uint8_t>(0), st.dev<uint8_t>(1), st.dev<uint8_t>(2),
+                          st.dev<uint8_t>(3), st.dev<uint8_t>(4), st.dev(5), st.dev<int32_t>(6), st.dev<int32_t>(7),
+                          st.dev<uint8_t>(8), st.dev<uint8_t>(9), nullptr};
         enqueue_relay(G, precision, a, L, kind, s);
-        for (const Reg& r : outr)
-            if (r.bytes) hip_check(hipMemcpyAsync(r.host, dptr(r), r.bytes, hipMemcpyDeviceToHost, s), "D2H relay output");
-        hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        st.finish(3, s);
     });
 }
 
@@ -1265,12 +1224,7 @@ int64_t qd_kernel_table_names(char* buf, int64_t cap) {
         std::string s;
         append_wave_kernel_names(s);
         append_block_kernel_names(s);
-        len = (int64_t)s.size();
-        if (buf && cap > 0) {
-            const size_t k = std::min<size_t>(s.size(), (size_t)cap - 1);
-            std::memcpy(buf, s.data(), k);
-            buf[k] = 0;
-        }
+        len = put_name(s, buf, cap);
     });
     return e ? e : len;
 }

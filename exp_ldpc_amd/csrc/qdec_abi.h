@@ -1,7 +1,8 @@
 // qdec_abi.h -- what the two ABI units (qdec_abi.cpp: graph handles;
 // qdec_abi_circuit.cpp: compiled circuits) share: HIP error checks, the guard
 // that keeps C++ exceptions inside the library, the device backends of
-// TableSink and ScratchMem, and the stream chain of a handle's buffers.
+// TableSink and ScratchMem, the stream chain of a handle's buffers, and the
+// staging of a host-buffer batch through a handle's workspace.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -133,6 +134,37 @@ struct DevBuf {
         cap = 0;
         hip_check(hipMalloc(&p, bytes), alloc_what);
         cap = c;
+    }
+};
+
+// One host-buffer batch staged through a handle's workspace: the regions
+// (StageRegions, inputs first), the workspace regrown once when they do not fit,
+// copies in, and behind the launch the copies out and the stream synchronise.
+// No drain before the regrow: every host entry point ends in that synchronise,
+// so the workspace has no user left.
+struct HostStage : StageRegions {
+    uint8_t* w = nullptr;
+    void place(DevBuf& ws) {
+        if (total > ws.cap) ws.regrow(total, total, "hipFree", "hipMalloc workspace", [] {});
+        w = static_cast<uint8_t*>(ws.p);
+    }
+    template <typename P = void>
+    P* dev(int r) const {  // null for a region that was not passed
+        return regs[r].bytes ? reinterpret_cast<P*>(w + regs[r].off) : nullptr;
+    }
+    // regions [first, last) host -> device (in) or device -> host; errors read "H2D <name>" / "D2H <name>"
+    void copy(int first, int last, bool in, hipStream_t s) const {
+        for (int r = first; r < last; ++r) {
+            const Reg& g = regs[r];
+            if (!g.bytes) continue;
+            const hipError_t e = in ? hipMemcpyAsync(w + g.off, g.host, g.bytes, hipMemcpyHostToDevice, s)
+                                    : hipMemcpyAsync(g.host, w + g.off, g.bytes, hipMemcpyDeviceToHost, s);
+            if (e != hipSuccess) hip_check(e, ((in ? "H2D " : "D2H ") + std::string(g.name)).c_str());
+        }
+    }
+    void finish(int first_out, hipStream_t s) const {
+        copy(first_out, (int)regs.size(), false, s);
+        hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
     }
 };
 

@@ -12,11 +12,8 @@ namespace qdec {
 // ---- bp_block_kernel and the workgroup SSF kernels
 constexpr int kBlock = 256;
 
-// Every block kernel starts its dynamic LDS with a 64-byte control area (no
-// static __shared__, so the dynamic base stays 16-byte aligned):
-//   [0, 32) long long red64[4]   [32, 48) int red32[4]   [48, 52) int slot
-//   [56, 64) long long next shot (dynamic shot counter)
-constexpr int kCtrl = 64;
+// Every block kernel starts its dynamic LDS with the control area of
+// qdec_graph.h (kCtrl bytes; fields kCtrlRed64, kCtrlRed32, kCtrlSlot, kCtrlNext).
 
 // control area + xh + one or two m_pad byte arrays + logical parities
 __host__ __device__ inline size_t block_small_lds(const DevGraph& g) {

@@ -14,34 +14,10 @@
 // path, with generators spread over the workgroup's threads.
 #include <hip/hip_runtime.h>
 
-#include "qdec_block_layout.h"
-#include "qdec_device.h"
+#include "qdec_block_steps.h"
 #include "qdec_kernels.h"
 
 namespace qdec {
-
-// block-wide sum / max through the control area (all threads must call)
-__device__ long long block_max_i64(long long v, long long* red) {
-    v = wave_max_i64(v);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    long long r = red[0];
-    for (int i = 1; i < kBlock / 64; ++i) r = red[i] > r ? red[i] : r;
-    __syncthreads();
-    return r;
-}
-
-__device__ int block_sum_i32(int v, int* red) {
-    v = wave_sum_i32(v);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    int r = 0;
-    for (int i = 0; i < kBlock / 64; ++i) r += red[i];
-    __syncthreads();
-    return r;
-}
 
 // dst[0..len) = src[0..len) (byte arrays, thread-strided), eight loads per
 // thread issued before the stores; returns this thread's sum of the bytes
@@ -192,7 +168,7 @@ __global__ __launch_bounds__(kBlock) void bp_block_kernel(DevGraph g, DecodeArgs
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int E = g.E, m = g.m, n = g.n, tid = threadIdx.x;
     constexpr int PREC = sizeof(T) == 4 ? 1 : 0;
-    int* slot_s = reinterpret_cast<int*>(smem + 48);
+    int* slot_s = reinterpret_cast<int*>(smem + kCtrlSlot);
     // placement bit 0: messages in LDS, bit 1: per-shot byte arrays in LDS;
     // whatever is not in LDS lives in this workgroup's HBM scratch slice
     const size_t msg_bytes = ((size_t)2 * E * sizeof(T) + 15) / 16 * 16;
@@ -233,28 +209,13 @@ __global__ __launch_bounds__(kBlock) void bp_block_kernel(DevGraph g, DecodeArgs
     const bool xb = DRM > 0 && placement == 0;
 
     // next shot: from the launcher's counter (dynamic, a.work_ctr) or by stride
-    long long* next_s = reinterpret_cast<long long*>(smem + 56);
+    long long* next_s = reinterpret_cast<long long*>(smem + kCtrlNext);
     auto next_shot = [&](int64_t cur) -> int64_t {
         if (!a.work_ctr) return cur < 0 ? (int64_t)blockIdx.x : cur + gridDim.x;
-        if (tid == 0) *next_s = (long long)atomicAdd(a.work_ctr, 1ull);
-        __syncthreads();
-        const int64_t s = *next_s;
-        __syncthreads();  // every thread has read it before the next overwrite
-        return s;
+        return block_next_shot(a.work_ctr, next_s, tid);
     };
     for (int64_t shot = next_shot(-1); shot < a.B; shot = next_shot(shot)) {
-        for (int i = tid; i < m; i += kBlock) {
-            int s = a.syn ? (a.syn[shot * m + i] & 1) : 0;
-            if (a.syn_flags) {
-                for (int e = rp[i]; e < rp[i + 1]; ++e) {
-                    const int j = ci[e];
-                    if (j >= g.n_data) continue;
-                    if ((a.syn_flags & 1) && a.base) s ^= a.base[shot * g.n_data + j] & 1;
-                    if ((a.syn_flags & 2) && a.readout) s ^= a.readout[shot * g.n_data + j] & 1;
-                }
-            }
-            sb[i] = (uint8_t)s;
-        }
+        block_syndrome_rows(sb, a.syn, a.syn_flags, a.base, a.readout, shot, g.n_data, rp, ci, m, tid);
         if (vcsc) {
             for (int j = tid; j < n; j += kBlock) {
                 const T pj = prior[j];
@@ -294,21 +255,7 @@ __global__ __launch_bounds__(kBlock) void bp_block_kernel(DevGraph g, DecodeArgs
                             c2v[vcsc ? e0 + t : ecs[e0 + t]] = (par ^ (v[t] <= (T)0)) ? -y : y;
                         }
                 } else if constexpr (METHOD == 1) {
-                    T m1 = Big<T>::v, m2 = Big<T>::v;
-                    int par = sb[i];
-                    for (int e = e0; e < e1; ++e) {
-                        const T v = v2c[e];
-                        const T av = fabs(v);
-                        m2 = med3(av, m1, m2);
-                        m1 = fmin(m1, av);
-                        par ^= v <= (T)0;
-                    }
-                    const T m1a = m1 * alpha, m2a = m2 * alpha;
-                    for (int e = e0; e < e1; ++e) {
-                        const T v = v2c[e];
-                        const T y = (fabs(v) == m1) ? m2a : m1a;
-                        c2v[e] = (par ^ (v <= (T)0)) ? -y : y;
-                    }
+                    ms_check_row(v2c, c2v, e0, e1, (int)sb[i], alpha);
                 } else if constexpr (DRM > 0) {
                     // product-sum, unrolled: forward products, then backward
                     const int d = e1 - e0;
@@ -440,10 +387,11 @@ __global__ __launch_bounds__(kBlock) void bp_block_kernel(DevGraph g, DecodeArgs
                 }
             }
             __syncthreads();
-            int bad = 0;
-            for (int i = tid; i < m; i += kBlock) {
-                int par = sb[i];
-                if constexpr (DRM > 0) {
+            bool open;
+            if constexpr (DRM > 0) {
+                int bad = 0;
+                for (int i = tid; i < m; i += kBlock) {
+                    int par = sb[i];
                     const int e0 = rp[i], d = rp[i + 1] - e0;
                     int cc[DRM];
 #pragma unroll
@@ -452,13 +400,14 @@ __global__ __launch_bounds__(kBlock) void bp_block_kernel(DevGraph g, DecodeArgs
 #pragma unroll
                     for (int t = 0; t < DRM; ++t)
                         if (t < d) par ^= xb ? (int)((xbits[cc[t] >> 6] >> (cc[t] & 63)) & 1ull) : (int)xh[cc[t]];
-                } else {
-                    for (int e = rp[i]; e < rp[i + 1]; ++e) par ^= xh[ci[e]];
+                    rs[i] = (uint8_t)par;
+                    bad |= par;
                 }
-                rs[i] = (uint8_t)par;
-                bad |= par;
+                open = __syncthreads_or(bad) != 0;
+            } else {
+                open = block_syndrome_open(sb, xh, rp, ci, m, tid, rs);
             }
-            if (!__syncthreads_or(bad)) {
+            if (!open) {
                 conv = true;
                 break;
             }
@@ -502,8 +451,8 @@ __global__ __launch_bounds__(kBlock) void bp_block_kernel(DevGraph g, DecodeArgs
 // exceeds the LDS budget, e.g. the 1.2*10^5-column spacetime graph of config 5).
 __global__ __launch_bounds__(kBlock) void ssf_block_kernel(DevGraph g, DecodeArgs a, unsigned char* gstate) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    long long* redl = reinterpret_cast<long long*>(smem);
-    int* redi = reinterpret_cast<int*>(smem + 32);
+    long long* redl = reinterpret_cast<long long*>(smem + kCtrlRed64);
+    int* redi = reinterpret_cast<int*>(smem + kCtrlRed32);
     uint8_t* xh = gstate ? gstate + (size_t)blockIdx.x * block_state_stride(g) : smem + kCtrl;  // [n_pad]
     uint8_t* sres = xh + g.n_pad;     // [m_pad]
     int* lpar = reinterpret_cast<int*>(sres + g.m_pad);  // [k]
@@ -520,7 +469,7 @@ __global__ __launch_bounds__(kBlock) void ssf_block_kernel(DevGraph g, DecodeArg
         // each one: ~40 HBM round trips per shot at n = 10^4)
         copy_bytes8(a.q_x + (int64_t)slot * n, xh, n, tid);
         int wl = copy_bytes8(a.q_r + (int64_t)slot * m, sres, m, tid);
-        int sw = block_sum_i32(wl, redi);  // includes a barrier: LDS fills visible
+        int sw = block_sum(wl, redi, tid);  // includes a barrier: LDS fills visible
         int steps = 0;
         while (a.ssf && sw > 0 && (a.ssf_max_steps <= 0 || steps < a.ssf_max_steps)) {
             long long best = LLONG_MIN;
@@ -534,7 +483,7 @@ __global__ __launch_bounds__(kBlock) void ssf_block_kernel(DevGraph g, DecodeArg
                 for (int k = 0; k < kGenW; ++k) qm[k] = g.g_qmask[k * g.g_pad + gi];
                 best = max(best, gen_key64(gen_best_key(sl, qm, nhi), gi));
             }
-            best = block_max_i64(best, redl);
+            best = block_max(best, redl, tid);
             const int score = (int)(best >> 32);
             if (best == LLONG_MIN || score <= 0) break;
             const int gsel = 0xFFFFFF - (int)((best >> 8) & 0xFFFFFF);
@@ -564,9 +513,9 @@ __global__ __launch_bounds__(kBlock) void ssf_block_kernel(DevGraph g, DecodeArg
 // afterwards by wave 0 (as in ssf_wave_kernel).
 __global__ __launch_bounds__(kBlock) void ssf_inc_block_kernel(DevGraph g, DecodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    long long* redl = reinterpret_cast<long long*>(smem);
-    int* redi = reinterpret_cast<int*>(smem + 32);
-    int* ctl = reinterpret_cast<int*>(smem + 48);  // [0] dirty count, [1] chosen subset
+    long long* redl = reinterpret_cast<long long*>(smem + kCtrlRed64);
+    int* redi = reinterpret_cast<int*>(smem + kCtrlRed32);
+    int* ctl = reinterpret_cast<int*>(smem + kCtrlSlot);  // [0] dirty count, [1] chosen subset, [2] its gain
     const size_t gp = (size_t)g.g_pad;
     int* key = reinterpret_cast<int*>(smem + kCtrl);
     uint32_t* slg = reinterpret_cast<uint32_t*>(key + gp);
@@ -646,7 +595,7 @@ __global__ __launch_bounds__(kBlock) void ssf_inc_block_kernel(DevGraph g, Decod
             copy_bytes8(a.q_x + (int64_t)slot * n, xh, n, tid);
             wl = copy_bytes8(a.q_r + (int64_t)slot * m, sres, m, tid);
         }
-        int sw = block_sum_i32(wl, redi);  // includes a barrier: LDS fills visible
+        int sw = block_sum(wl, redi, tid);  // includes a barrier: LDS fills visible
         int steps = 0;
         if (a.ssf && sw > 0) {
             for (int gi = tid; gi < ng; gi += kBlock) {
@@ -660,7 +609,7 @@ __global__ __launch_bounds__(kBlock) void ssf_inc_block_kernel(DevGraph g, Decod
             while (sw > 0 && (a.ssf_max_steps <= 0 || steps < a.ssf_max_steps)) {
                 long long best = LLONG_MIN;
                 for (int gi = tid; gi < ng; gi += kBlock) best = max(best, (long long)key[gi]);
-                best = block_max_i64(best, redl);
+                best = block_max(best, redl, tid);
                 const int kv = (int)best;
                 const int score = kv >> 13;
                 if (best == LLONG_MIN || kv == INT_MIN || score <= 0) break;

@@ -141,6 +141,32 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
     return v;
 }
 
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// The syndrome bit of row i of a shot, for every stage that decodes from the
+// caller's rows (BP and relay workgroup kernels, the OSD kernels): syn_bit,
+// xor syn_term of every entry j of the row, which is the base / readout bit of
+// a data column as syn_flags asks (bit 0 base, bit 1 readout).  syn_term takes
+// references, so a kernel passes fields of its arguments and they are read
+// where the bit is needed: the OSD kernels' code is what their own copy gave.
+__device__ __forceinline__ int syn_bit(const uint8_t* syn, int64_t shot, int m, int i) {
+    return syn ? (syn[shot * m + i] & 1) : 0;
+}
+
+__device__ __forceinline__ int syn_term(const int& syn_flags, const uint8_t* const& base,
+                                        const uint8_t* const& readout, int64_t shot, const int& n_data, int j) {
+    int sb = 0;
+    if (syn_flags && j < n_data) {
+        if ((syn_flags & 1) && base) sb ^= base[shot * n_data + j] & 1;
+        if ((syn_flags & 2) && readout) sb ^= readout[shot * n_data + j] & 1;
+    }
+    return sb;
+}
+
 // median of three with lo <= hi: clamp(a, lo, hi) = min(hi, max(lo, a))
 __device__ __forceinline__ float med3(float a, float lo, float hi) { return __builtin_amdgcn_fmed3f(a, lo, hi); }
 __device__ __forceinline__ double med3(double a, double lo, double hi) { return fmin(hi, fmax(lo, a)); }

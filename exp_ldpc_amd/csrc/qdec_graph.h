@@ -22,6 +22,15 @@ constexpr int kCmpLists = 2;     // the light list (segments 0..63) and the heav
 // entries a compact-list segment must hold for a batch of B shots (64-shot tiles)
 inline int64_t cmp_seg_cap(int64_t B) { return ((B + 63) / 64 + kCmpSegs - 1) / kCmpSegs * 64; }
 
+// Every workgroup kernel starts its dynamic LDS with a control area of kCtrl
+// bytes (no static __shared__, so the dynamic base stays 16-byte aligned).
+// Byte offsets of its fields; a kernel's own arrays start at kCtrl.
+constexpr int kCtrlRed64 = 0;   // long long [4]: per-wave partials of a 64-bit block reduction
+constexpr int kCtrlRed32 = 32;  // int [4]: the same for a 32-bit one
+constexpr int kCtrlSlot = 48;   // int: a queue slot; ssf_inc_block_kernel's int ctl[3], which has no shot counter
+constexpr int kCtrlNext = 56;   // long long: the shot counter's answer
+constexpr int kCtrl = 64;
+
 // Wave-kernel shapes (check rounds RC, variable rounds RV, check-node compute
 // width D <= kDR): a graph is padded to the first shape that holds it (RC*64 >= m,
 // RV*64 >= n, D >= max check degree), and the kernel is instantiated for exactly

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kMlThreads) void bp_ms_lds_kernel(DevGraph g, Decod
                                                               const float* __restrict__ img) {
     static_assert(VPT * 3 <= 64 && VPT <= 32, "degree and decision bits");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    long long* next = reinterpret_cast<long long*>(smem + 56);
+    long long* next = reinterpret_cast<long long*>(smem + kCtrlNext);
     float* rows = reinterpret_cast<float*>(smem + kCtrl);
     const int tid = threadIdx.x;
     const int m = g.m, n = g.n;

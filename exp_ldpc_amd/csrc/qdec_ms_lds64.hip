@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kM64Threads) void bp_ms_lds64_kernel(DevGraph g, De
                                                                  const unsigned long long* __restrict__ img) {
     static_assert(VPT * 3 <= 32 && VPT <= 32 && D3R <= VPT, "degree and decision bits");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    long long* next = reinterpret_cast<long long*>(smem + 56);
+    long long* next = reinterpret_cast<long long*>(smem + kCtrlNext);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int m = g.m, n = g.n;
     const int W = (int)m64_words(g);

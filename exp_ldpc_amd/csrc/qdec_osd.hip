@@ -143,11 +143,11 @@ __global__ __launch_bounds__(64) void osd_wave_kernel(DevGraph g, OsdArgs a) {
             for (int w = 0; w < W; ++w) row[s][w] = 0;
             const int i = s * 64 + lane;
             if (i < m) {
-                int sb = osd_syn_bit(a, shot, m, i);
+                int sb = syn_bit(a.syn, shot, m, i);
                 for (int e = rp[i]; e < rp[i + 1]; ++e) {
                     const int j = ci[e];
                     flip_bit<W>(row[s], pos[j]);
-                    sb ^= osd_syn_term(g, a, shot, j);
+                    sb ^= syn_term(a.syn_flags, a.base, a.readout, shot, g.n_data, j);
                 }
                 if (sb) flip_bit<W>(row[s], n);
             }
@@ -422,12 +422,12 @@ __global__ __launch_bounds__(kOsdBlock) void osd_block_kernel(DevGraph g, OsdArg
         // ---- 2. augmented rows [H_sorted | s] (one thread per row)
         for (int i = tid; i < m; i += kOsdBlock) {
             uint64_t* r = A + (size_t)i * W;
-            int sb = osd_syn_bit(a, shot, m, i);
+            int sb = syn_bit(a.syn, shot, m, i);
             for (int e = rp[i]; e < rp[i + 1]; ++e) {
                 const int j = ci[e];
                 const int k = pos[j];
                 r[k >> 6] ^= 1ull << (k & 63);
-                sb ^= osd_syn_term(g, a, shot, j);
+                sb ^= syn_term(a.syn_flags, a.base, a.readout, shot, g.n_data, j);
             }
             if (sb) r[n >> 6] ^= 1ull << (n & 63);
         }

@@ -164,13 +164,13 @@ __global__ __launch_bounds__(kHbmBlock) void osd_hbm_kernel(DevGraph g, OsdArgs 
             for (int i = wave; i < m; i += kHbmWaves) {
                 for (int w = lane; w < W; w += 64) rb[w] = 0;
                 __builtin_amdgcn_wave_barrier();  // one wave: LDS operations complete in order
-                int sb = lane == 0 ? osd_syn_bit(a, shot, m, i) : 0;
+                int sb = lane == 0 ? syn_bit(a.syn, shot, m, i) : 0;
                 for (int e = rp[i] + lane; e < rp[i + 1]; e += 64) {
                     const int j = ci[e];
                     const uint32_t k = pos[j];
                     if (k >= (uint32_t)n) continue;
                     atomicXor(reinterpret_cast<unsigned long long*>(&rb[k >> 6]), 1ull << (k & 63));
-                    sb ^= osd_syn_term(g, a, shot, j);
+                    sb ^= syn_term(a.syn_flags, a.base, a.readout, shot, g.n_data, j);
                 }
                 const int par = __popcll(__ballot(sb & 1)) & 1;
                 if (lane == 0 && par) atomicXor(reinterpret_cast<unsigned long long*>(&rb[n >> 6]), 1ull << (n & 63));

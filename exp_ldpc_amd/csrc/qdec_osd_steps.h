@@ -105,20 +105,8 @@ __device__ __forceinline__ void bitonic_sort_lds(uint64_t* key, Idx* idx, int NS
         }
 }
 
-// ---- 2. the syndrome bit of row i: syn, and per entry of the row on a data
-// column j the base / readout bit that syn_flags asks for
-__device__ __forceinline__ int osd_syn_bit(const OsdArgs& a, int64_t shot, int m, int i) {
-    return a.syn ? (a.syn[shot * m + i] & 1) : 0;
-}
-
-__device__ __forceinline__ int osd_syn_term(const DevGraph& g, const OsdArgs& a, int64_t shot, int j) {
-    int sb = 0;
-    if (a.syn_flags && j < g.n_data) {
-        if ((a.syn_flags & 1) && a.base) sb ^= a.base[shot * g.n_data + j] & 1;
-        if ((a.syn_flags & 2) && a.readout) sb ^= a.readout[shot * g.n_data + j] & 1;
-    }
-    return sb;
-}
+// ---- 2. the syndrome bit of a row: syn_bit / syn_term of qdec_device.h, the
+// rule the BP stages build their rows by
 
 // ---- 4. the first `want` non-pivot positions, ascending (one wave); returns
 // how many the positions walked hold, all of them when want >= n

@@ -49,7 +49,7 @@ struct RelayArgs {
     unsigned long long* work_ctr;  // the launch's shot counter, zeroed before it
 };
 
-// Byte offsets.  LDS: the control area (kCtrl of the block kernels), the hard
+// Byte offsets.  LDS: the control area (kCtrl of qdec_graph.h), the hard
 // decision and the syndrome as bytes, the best solution as bits; with the
 // messages in LDS they follow at l_msg.  The message region (LDS, or one slot
 // of the scratch): v2c[E], c2v[E] by CSR edge, then the marginals M[n].
@@ -59,7 +59,7 @@ struct RelayLayout {
     RelayLayout() = default;
     RelayLayout(const DevGraph& g, int64_t tsz) {
         auto r16 = [](int64_t b) { return (b + 15) / 16 * 16; };
-        l_xh = 64;
+        l_xh = kCtrl;
         l_sb = l_xh + g.n_pad;
         l_best = l_sb + g.m_pad;
         l_msg = lds_small = r16(l_best + (int64_t)g.n_pad / 8);

@@ -18,27 +18,13 @@
 // come through vector loads and stay in L2 across the workgroups.
 #include <hip/hip_runtime.h>
 
-#include "qdec_block_layout.h"
-#include "qdec_device.h"
+#include "qdec_block_steps.h"
 #include "qdec_kernels.h"
 #include "qdec_relay.h"
 
 namespace qdec {
 
 namespace {
-
-// block-wide sum through the control area (all threads must call)
-__device__ long long relay_block_sum(long long v, long long* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    long long r = 0;
-    for (int i = 0; i < kBlock / 64; ++i) r += red[i];
-    __syncthreads();
-    return r;
-}
 
 template <typename T>
 __device__ __forceinline__ T clamp_to(T v, T clip) {
@@ -53,8 +39,8 @@ __global__ __launch_bounds__(kBlock) void relay_block_kernel(DevGraph g, RelayAr
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int PREC = sizeof(T) == 4 ? 1 : 0;
     const int E = g.E, m = g.m, n = g.n, tid = threadIdx.x;
-    long long* red = reinterpret_cast<long long*>(smem);          // [4]
-    long long* next_s = reinterpret_cast<long long*>(smem + 56);  // the shot counter's answer
+    long long* red = reinterpret_cast<long long*>(smem + kCtrlRed64);
+    long long* next_s = reinterpret_cast<long long*>(smem + kCtrlNext);
     uint8_t* xh = smem + L.l_xh;                                  // [n_pad] hard decision
     uint8_t* sb = smem + L.l_sb;                                  // [m_pad] syndrome bits
     uint64_t* best = reinterpret_cast<uint64_t*>(smem + L.l_best);  // [n_pad / 64] best solution
@@ -71,27 +57,10 @@ __global__ __launch_bounds__(kBlock) void relay_block_kernel(DevGraph g, RelayAr
     const T alpha = (T)rt.alpha, clip = (T)rt.clip;
     (void)E;
 
-    auto next_shot = [&]() -> int64_t {
-        if (tid == 0) *next_s = (long long)atomicAdd(a.work_ctr, 1ull);
-        __syncthreads();
-        const int64_t s = *next_s;
-        __syncthreads();  // every thread has read it before the next overwrite
-        return s;
-    };
-    for (int64_t shot = next_shot(); shot < a.B; shot = next_shot()) {
+    for (int64_t shot = block_next_shot(a.work_ctr, next_s, tid); shot < a.B;
+         shot = block_next_shot(a.work_ctr, next_s, tid)) {
         if (a.only_failed && a.status && (a.status[shot] & 1)) continue;  // uniform over the workgroup
-        for (int i = tid; i < m; i += kBlock) {
-            int s = a.syn ? (a.syn[shot * m + i] & 1) : 0;
-            if (a.syn_flags) {
-                for (int e = rp[i]; e < rp[i + 1]; ++e) {
-                    const int j = ci[e];
-                    if (j >= g.n_data) continue;
-                    if ((a.syn_flags & 1) && a.base) s ^= a.base[shot * g.n_data + j] & 1;
-                    if ((a.syn_flags & 2) && a.readout) s ^= a.readout[shot * g.n_data + j] & 1;
-                }
-            }
-            sb[i] = (uint8_t)s;
-        }
+        block_syndrome_rows(sb, a.syn, a.syn_flags, a.base, a.readout, shot, g.n_data, rp, ci, m, tid);
         for (int j = tid; j < n; j += kBlock) M[j] = prior[j];
         __syncthreads();
         int found = 0, legs = 0, iters = 0;
@@ -109,24 +78,7 @@ __global__ __launch_bounds__(kBlock) void relay_block_kernel(DevGraph g, RelayAr
             __syncthreads();
             bool conv = false;
             for (int it = 1; it <= leg_iter; ++it) {
-                for (int i = tid; i < m; i += kBlock) {
-                    const int e0 = rp[i], e1 = rp[i + 1];
-                    T m1 = Big<T>::v, m2 = Big<T>::v;
-                    int par = sb[i];
-                    for (int e = e0; e < e1; ++e) {
-                        const T v = v2c[e];
-                        const T av = fabs(v);
-                        m2 = med3(av, m1, m2);
-                        m1 = fmin(m1, av);
-                        par ^= v <= (T)0;
-                    }
-                    const T m1a = m1 * alpha, m2a = m2 * alpha;
-                    for (int e = e0; e < e1; ++e) {
-                        const T v = v2c[e];
-                        const T y = (fabs(v) == m1) ? m2a : m1a;
-                        c2v[e] = (par ^ (v <= (T)0)) ? -y : y;
-                    }
-                }
+                for (int i = tid; i < m; i += kBlock) ms_check_row(v2c, c2v, rp[i], rp[i + 1], (int)sb[i], alpha);
                 __syncthreads();
                 for (int j = tid; j < n; j += kBlock) {
                     const int t0 = cp[j], t1 = cp[j + 1];
@@ -148,14 +100,8 @@ __global__ __launch_bounds__(kBlock) void relay_block_kernel(DevGraph g, RelayAr
                     }
                 }
                 __syncthreads();
-                int bad = 0;
-                for (int i = tid; i < m; i += kBlock) {
-                    int par = sb[i];
-                    for (int e = rp[i]; e < rp[i + 1]; ++e) par ^= xh[ci[e]];
-                    bad |= par;
-                }
                 ++iters;
-                if (!__syncthreads_or(bad)) {
+                if (!block_syndrome_open(sb, xh, rp, ci, m, tid, nullptr)) {
                     conv = true;
                     break;
                 }
@@ -166,7 +112,7 @@ __global__ __launch_bounds__(kBlock) void relay_block_kernel(DevGraph g, RelayAr
             long long wl = 0;
             for (int j = tid; j < n; j += kBlock)
                 if (xh[j]) wl += rt.w[j];
-            const long long wgt = relay_block_sum(wl, red);
+            const long long wgt = block_sum(wl, red, tid);
             if (!have_best || wgt < best_w) {  // uniform; a tie keeps the earlier leg
                 have_best = true;
                 best_w = wgt;

@@ -1,7 +1,8 @@
 // qdec_scratch.h -- the policy of the scratch areas that shrink when device
 // memory is short: the slot scratches of osd_hbm_kernel and of the HBM-placed
 // Pauli-frame kernels (SlotScratch) and the HBM message scratch of the workgroup
-// BP kernels (MessageScratch).  Pure host code with no HIP header: the memory
+// BP kernels (MessageScratch); and the region layout of a host-buffer batch in
+// the workspace (StageRegions).  Pure host code with no HIP header: the memory
 // comes through a ScratchMem, which the library backs with HIP (qdec_abi.h) and
 // the stand-alone checker (tools/scratch_check.cpp) with a fake that refuses.
 #pragma once
@@ -141,6 +142,24 @@ struct MessageScratch : ScratchBuf {
             *got = bytes;
         }
         return ptr;
+    }
+};
+
+// The regions of one host-buffer batch in a handle's workspace, in the order
+// they are added: 256-B aligned, and none for a null host pointer (its device
+// pointer is null too).  `name` is the region's in the copies' error texts.
+struct StageRegions {
+    struct Reg {
+        size_t off, bytes;
+        void* host;
+        const char* name;
+    };
+    std::vector<Reg> regs;
+    size_t total = 0;  // bytes of workspace the regions need
+    int add(const void* host, size_t bytes, const char* name) {
+        regs.push_back({total, host ? bytes : 0, const_cast<void*>(host), name});
+        if (host) total += (bytes + 255) / 256 * 256;
+        return (int)regs.size() - 1;
     }
 };
 

@@ -26,6 +26,14 @@ def graph(name):
     """-> dict(H, n_data, fold_blocks, lz, probs)."""
     if name == "h35":
         H, n_data, fb, lz = sp.csr_matrix(H35), 5, 1, np.array([[1, 0, 1, 0, 1]], np.uint8)
+    elif name == "h35w17":
+        # the 3 x 5 graph and one check of weight 17 on columns 4 .. 20 (4 x 21): the
+        # smallest row past the unrolled 16, 8 instantiation of bp_block_kernel and
+        # outside the wave shapes, so plain BP runs the generic <T, 1, *, 0, 0>
+        Hw = np.zeros((4, 21), np.uint8)
+        Hw[:3, :5] = H35
+        Hw[3, 4:] = 1
+        H, n_data, fb, lz = sp.csr_matrix(Hw), 21, 1, (np.arange(21)[None, :] % 3 == 0).astype(np.uint8)
     elif name == "hz225":
         code = load_code("hgp_12_3_4_s1234")
         H, n_data, fb, lz = sp.csr_matrix(code.checks.z), 225, 1, np.asarray(code.logicals.z) % 2
@@ -45,7 +53,7 @@ def graph(name):
     return dict(H=H, n_data=n_data, fold_blocks=fb, lz=lz.astype(np.uint8), probs=probs)
 
 
-GRAPHS = ("h35", "hz225", "st225r2", "bb144")
+GRAPHS = ("h35", "h35w17", "hz225", "st225r2", "bb144")
 # name -> relay parameters and the interval the strengths are drawn from
 PARAM_SETS = {
     "mix": dict(gamma0=0.125, pre_iter=8, num_sets=4, set_max_iter=8, stop_nconv=2, alpha=1.0, clip=2.0 ** 64,
@@ -60,8 +68,9 @@ PARAM_SETS = {
                  interval=(-0.5, 1.5)),
 }
 # seeds of the B = 64 "mix" batch per graph, good in both precisions (chosen
-# with the model; the 3 x 5 graph is too small to hold all four kinds)
-MIX_SEED = {"h35": 0, "hz225": 4, "st225r2": 84, "bb144": 1}
+# with the model; the 3 x 5 graph and its 4 x 21 extension are too small to
+# hold all four kinds)
+MIX_SEED = {"h35": 0, "h35w17": 0, "hz225": 4, "st225r2": 84, "bb144": 1}
 
 
 def relay_kwargs(gname, pset):
@@ -95,6 +104,29 @@ def shots(gname, B, seed):
     for t in range(g["fold_blocks"]):
         readout ^= e[:, t * g["n_data"]:(t + 1) * g["n_data"]]
     return syn, base, readout
+
+
+# The generic rows of bp_block_kernel and relay_block_kernel on "h35w17": min-sum,
+# max_iter = pre_iter, the same alpha.  Seeds chosen with the model so that in
+# both precisions some of the 8 shots converge and some stay open, with the
+# syndrome given (syn_flags 0) and derived from base and readout (syn_flags 3).
+WIDE_ROW = dict(B=8, seed=0, max_iter=3, alpha=0.625)
+
+
+def wide_row_shots(syn_flags):
+    """(syn or None, base, readout) of the WIDE_ROW batch."""
+    syn, base, rd = shots("h35w17", WIDE_ROW["B"], WIDE_ROW["seed"])
+    if syn_flags == 0:
+        return syn, base, rd
+    rng = np.random.default_rng(5)  # sparse rows, so the derived syndromes are decodable
+    return None, (rng.random(base.shape) < 0.05).astype(np.uint8), (rng.random(rd.shape) < 0.05).astype(np.uint8)
+
+
+def wide_row_model(dtype):
+    g = graph("h35w17")
+    # clip = inf: the degree-1 row sends Big, beyond any finite clip
+    return RelayModel(g["H"], g["probs"], dtype, gamma0=0.0, pre_iter=WIDE_ROW["max_iter"], num_sets=0,
+                      alpha=WIDE_ROW["alpha"], clip=np.inf, n_data=g["n_data"], fold_blocks=1, logicals=g["lz"])
 
 
 def mix_kinds(ref):

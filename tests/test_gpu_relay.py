@@ -1,6 +1,7 @@
 """relay_block_kernel against the numpy model (tests/relay_model.py), bit for bit:
 x, iters, legs, status, corr, fail and the bytes of llr, in both precisions and
-both placements, on the 3 x 5 graph, Hz of the n = 225 code, its R = 2 spacetime
+both placements, on the 3 x 5 graph, its 4 x 21 extension with a row of weight
+17 (bp_block_kernel's generic rows too), Hz of the n = 225 code, its R = 2 spacetime
 graph (324 x 891: the 256-thread strides wrap, fold_blocks 3) and the
 [[144,12,12]] Hz.  Graphs, parameter sets and seeds: tests/relay_cases.py."""
 import functools
@@ -51,7 +52,7 @@ def assert_equal(got, ref, rows=slice(None), what=""):
 def test_relay_matches_the_model_in_both_placements(gpu_available, gname, precision, pset):
     B, seed = 64, rc.MIX_SEED[gname]
     ref = reference(gname, precision, pset, B, seed)
-    if pset == "mix" and gname != "h35":
+    if pset == "mix" and not gname.startswith("h35"):
         kinds = rc.mix_kinds(ref)
         assert all(kinds.values()), kinds
     if pset == "clip":  # the small clip engages
@@ -150,7 +151,7 @@ def test_without_memory_relay_is_the_tested_min_sum_decode(gpu_available, gname,
     B = 32
     syn, base, rd = rc.shots(gname, B, 7)
     # a degree-1 row sends Big, beyond every finite clip: no clamp on the 3 x 5 graph
-    clip = np.inf if gname == "h35" else 2.0 ** 64
+    clip = np.inf if gname.startswith("h35") else 2.0 ** 64
     bp = Decoder(g["H"], g["probs"], method="ms", precision=precision, max_iter=pre_iter, ms_scaling=alpha,
                  logicals=g["lz"], n_data=g["n_data"], fold_blocks=g["fold_blocks"])
     dec = make_decoder(gname, precision, gamma0=0.0, num_sets=0, pre_iter=pre_iter, alpha=alpha, clip=clip,
@@ -164,6 +165,37 @@ def test_without_memory_relay_is_the_tested_min_sum_decode(gpu_available, gname,
                 assert np.array_equal(got[k], want[k]), (placement, k)
             assert got["llr"].tobytes() == want["llr"].tobytes(), placement
             assert (got["legs"] == 1).all()
+    finally:
+        bp.close()
+        dec.close()
+
+
+@pytest.mark.parametrize("syn_flags", [0, 3])
+@pytest.mark.parametrize("precision", ["f32", "f64"])
+def test_generic_rows_of_both_kernels_on_the_weight_17_row(gpu_available, precision, syn_flags):
+    """bp_block_kernel<T, 1, false, 0, 0> (the plan: test_relay_host.py) and
+    relay_block_kernel at gamma = 0 against the numpy model on "h35w17": x, iters
+    and the bytes of llr, with the syndrome given and derived from base and
+    readout; some shots converge and some stay open."""
+    from exp_ldpc_amd.decoder import Decoder
+    g, w = rc.graph("h35w17"), rc.WIDE_ROW
+    syn, base, rd = rc.wide_row_shots(syn_flags)
+    ref = rc.wide_row_model(DTYPES[precision]).decode(syn, base, rd, syn_flags)
+    assert 0 < (ref["status"] & 1).sum() < w["B"]
+    bp = Decoder(g["H"], g["probs"], method="ms", precision=precision, max_iter=w["max_iter"], ms_scaling=w["alpha"],
+                 logicals=g["lz"], n_data=g["n_data"], fold_blocks=g["fold_blocks"])
+    dec = make_decoder("h35w17", precision, gamma0=0.0, num_sets=0, pre_iter=w["max_iter"], alpha=w["alpha"],
+                       clip=np.inf, stop_nconv=1, gammas=None)
+    try:
+        runs = {"bp": bp.decode(syn, base=base, readout=rd, syn_flags=syn_flags, want=("x", "llr", "iters", "status"))}
+        for placement in ("lds", "hbm"):
+            runs[placement] = dec.relay(syn, base=base, readout=rd, syn_flags=syn_flags, placement=placement, want=WANT)
+        for name, got in runs.items():
+            print(name, got["iters"].tolist(), (got["status"] & 1).tolist())
+            assert np.array_equal(got["x"], ref["x"]), name
+            assert np.array_equal(got["iters"], ref["iters"]), name
+            assert np.array_equal(got["status"] & 1, ref["status"] & 1), name
+            assert got["llr"].dtype == ref["llr"].dtype and got["llr"].tobytes() == ref["llr"].tobytes(), name
     finally:
         bp.close()
         dec.close()

@@ -176,6 +176,36 @@ def test_relay_info_and_kernel_names(lib):
     assert "relay" not in big.value.decode()  # the decode families' list is pinned and unchanged
 
 
+def test_the_weight_17_row_plans_the_generic_block_kernel_and_its_shots_take_both_exits(lib):
+    """"h35w17" (tests/relay_cases.py): the launch plan puts plain min-sum BP in
+    the workgroup family (bp 5: bp_block_kernel) in both precisions.  That family
+    reports no kernel name (qd_graph_plan_names stays "" for it, as
+    qd_graph_last_kernels does), so the instantiation is pinned by the planner's
+    rule instead: a row above 16 entries rules out <T, 1, *, 16, 8> and leaves
+    <T, 1, *, 0, 0>.  And on the CPU: of the WIDE_ROW shots the model solves some
+    and leaves some open, so test_gpu_relay.py runs both exits of the loop."""
+    from exp_ldpc_amd import _abi
+    from host_helpers import _plan_names
+    g = rc.graph("h35w17")
+    assert np.diff(g["H"].indptr).max() == 17 and g["H"].shape == (4, 21)
+    h = host_graph(lib, g["H"], g["probs"])
+    try:
+        for prec in (_abi.QD_F64, _abi.QD_F32):
+            prm = _abi.QdParams(rc.WIDE_ROW["max_iter"], 1, prec, 0, 0, 0, rc.WIDE_ROW["alpha"])
+            for present in (1 | 4 | 64 | 128, 2 | 4 | 8 | 32 | 64):  # syn, readout, fail / base, readout, x, llr, fail
+                out = np.zeros(8, np.int32)
+                assert lib.qd_graph_plan(h, C.byref(prm), rc.WIDE_ROW["B"], present, _abi.ptr(out)) == 0
+                assert out[0] == 5 and out[1] == 0  # kBpBlock, no SSF stage
+                assert _plan_names(lib, h, prm, rc.WIDE_ROW["B"], present) == ["", "", ""]
+    finally:
+        lib.qd_graph_destroy(h)
+    for dtype in (np.float32, np.float64):
+        for flags in (0, 3):
+            syn, base, rd = rc.wide_row_shots(flags)
+            conv = rc.wide_row_model(dtype).decode(syn, base, rd, flags)["status"] & 1
+            assert 0 < conv.sum() < rc.WIDE_ROW["B"], (dtype, flags)
+
+
 # ---------------------------------------------------------------- 3. the gain over plain min-sum
 def test_relay_leaves_fewer_unsatisfied_shots_than_long_min_sum():
     """1000 code-capacity shots of the n = 225 code at p = 0.02 (numpy PCG64

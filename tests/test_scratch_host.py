@@ -1,7 +1,8 @@
 """The scratch policy (exp_ldpc_amd/csrc/qdec_scratch.h) under ASan + UBSan.
 
 tools/scratch_check.cpp drives the slot scratch (OSD and frame parameters) and
-the message scratch over a fake memory that refuses requests, with no HIP header
+the message scratch over a fake memory that refuses requests, and lays out the
+regions of a host-buffer batch (StageRegions), with no HIP header
 on the include path -- compiling it is the proof that the policy is HIP-free --
 and a static sanitizer runtime, so the program runs as an ordinary child process
 (this test sets up no preload).  It must exit 0, print no sanitizer report (the
@@ -77,6 +78,9 @@ EXPECTED = {
     "message_floor_refused": ["drain", "alloc 4000 oom", "-> - 0 0 -102 hipMalloc message scratch: out of memory",
                               "-> null 0 0 0",
                               "drain"],
+    # the regions of a host-buffer batch: each starts on the next 256 B, a null
+    # pointer takes no room (and no bytes), 300 + 256 + 1 B need 1024
+    "stage_regions": ["region a 0 300", "region b 512 0", "region c 512 256", "region d 768 1", "-> 1024"],
 }
 
 

@@ -174,5 +174,21 @@ int main() {
         message(s, 0, 0);
         s.release(mem, "hipFree scratch");
     }
+    {
+        begin("stage_regions");  // "region name offset bytes", then "-> total"; every region written whole
+        StageRegions st;
+        char h = 0;
+        st.add(&h, 300, "a");
+        st.add(nullptr, 5000, "b");
+        st.add(&h, 256, "c");
+        st.add(&h, 1, "d");
+        auto* w = static_cast<unsigned char*>(std::malloc(st.total));
+        for (const StageRegions::Reg& r : st.regs) {
+            std::printf("region %s %zu %zu\n", r.name, r.off, r.bytes);
+            std::memset(w + r.off, 0xab, r.bytes);
+        }
+        std::printf("-> %zu\n", st.total);
+        std::free(w);
+    }
     return 0;
 }
