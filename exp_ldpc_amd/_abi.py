@@ -128,6 +128,11 @@ SIGNATURES = {
     "qd_relay_set_slots": (_i32, [_p, _i64]),
     "qd_relay_info": (_i32, [_p, _i32, _i32, _p]),
     "qd_relay_kernel_names": (_i64, [C.c_char_p, _i64]),
+    "qd_window_create": (_i32, [_i32, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _p, _i32, _i32, C.POINTER(_p)]),
+    "qd_window_create_host": (_i32, [_i32, _i32, _i32, _p, _p, _p, _i32, _p, _p, _i32, _i32, C.POINTER(_p)]),
+    "qd_window_advance_device": (_i32, [_p, _i64, _p, _p, _p, _p, _p]),
+    "qd_window_set_blocks": (_i32, [_p, _i64]),
+    "qd_window_destroy": (_i32, [_p]),
     "qd_graph_set_option": (_i32, [_p, _i32, _i32]),
     "qd_graph_get_option": (_i32, [_p, _i32, C.POINTER(_i32)]),
     "qd_graph_ssf_tables": (_i32, [_p, C.POINTER(_i32), C.POINTER(_i64)]),

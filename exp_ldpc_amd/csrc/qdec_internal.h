@@ -13,6 +13,7 @@
 #include "qdec_circuit.h"
 #include "qdec_graph.h"
 #include "qdec_relay.h"
+#include "qdec_window.h"
 
 namespace qdec {
 
@@ -206,6 +207,10 @@ const KernelTable& relay_table();
 void append_relay_kernel_names(std::string& out);
 int launch_relay(const DevGraph& g, int precision, const RelayArgs& a, const RelayTables& t, const RelayLayout& L,
                  void* scratch, int64_t grid, hipStream_t stream);
+
+// window_advance_kernel (qdec_window.hip; tables and arguments: qdec_window.h):
+// `grid` workgroups take the B shots grid-strided.  Returns hipError_t as int.
+int launch_window(const WindowDev& w, const WindowArgs& a, int64_t grid, hipStream_t stream);
 
 // ---------------------------------------------------------------- launch plan
 // Everything a decode decides before its first launch, decided once

@@ -37,6 +37,11 @@ The relay stage's options travel in ``bp_osd_options`` under ``relay_*`` keys
 (add_relay_args / unpack_relay_args; Decoder.set_relay's arguments, plus
 ``relay_placement``) or in the pipelines' ``relay`` argument.
 
+``window=W`` (and ``commit=C``, by default max(1, W // 2)) makes ``bp`` and
+``bposd`` decode the rounds in sliding windows of W rounds that commit C at a
+time instead of on one graph over all rounds (window.py, csrc/qdec_window.hip;
+DESIGN 3.6e): every window has the same size whatever the round count is.
+
 OSD runs on the GPU for the shots BP did not converge on (Decoder.osd_device),
 fused with the fold and the failure check: csrc/qdec_osd.hip with the rows on
 chip, csrc/qdec_osd_hbm.hip with the rows in device memory.  ``osd_rows`` says
@@ -76,6 +81,7 @@ __all__ = ["DECODER_MODES", "BatchPipeline", "DemPipeline", "run_dem_simulation"
 DECODER_MODES = ["bposd", "bposd_single_shot", "bposd_hybrid", "bpd_detector", "bposd_detector", "bpssf",
                  "bpssf_hybrid", "bp", "bprelay", "bprelay_detector"]
 DETECTOR_MODES = ("bpd_detector", "bposd_detector", "bprelay_detector")
+WINDOW_MODES = ("bp", "bposd")  # the modes that take window= / commit=
 # Decoder.set_relay's arguments, as relay_<name> keys of bp_osd_options
 RELAY_KEYS = ("gamma0", "pre_iter", "num_sets", "set_max_iter", "gamma_dist_interval", "stop_nconv", "alpha", "clip",
               "seed", "gammas")
@@ -322,9 +328,19 @@ class BatchPipeline:
                  device: int = 0, precision: str = "f64", use_x_logicals: bool = False, osd_threads: int = 0,
                  noise=None, dem_source: str | None = None, sim=None, osd_rows: str | None = None,
                  llr_budget_bytes: int = DEFAULT_LLR_BUDGET, approximate_disjoint_errors: bool = False,
-                 relay: Dict | None = None):
+                 relay: Dict | None = None, window: int | None = None, commit: int | None = None):
         if mode not in DECODER_MODES:
             raise RuntimeError("Unknown decoder operation mode")
+        if window is None and commit is not None:
+            raise ValueError("commit applies to a windowed decode only (window=...)")
+        if window is not None:
+            # sliding-window decoding (window.py): bp and bposd only
+            from .window import check_window_args
+            if mode not in WINDOW_MODES:
+                raise ValueError(f"window applies to the decoder modes {WINDOW_MODES} only, got {mode!r}")
+            window, commit = check_window_args(window, commit)
+        self.window, self.commit = window, commit
+        self.wd = None
         if dem_source not in (None, "circuit"):
             raise ValueError('dem_source is None (by noise model) or "circuit"')
         if dem_source is not None and mode not in DETECTOR_MODES:
@@ -370,7 +386,16 @@ class BatchPipeline:
             prior = np.empty(Hst.shape[1])
             prior[st.true_data_slice()] = data_prior
             prior[(R + 1) * n:] = meas_prior
-            self.st = Decoder(Hst, prior, n_data=n, fold_blocks=R + 1, logicals=lz, **common)
+            if window is not None:
+                # every non-final window on one shared graph, then the existing
+                # fused stage on the final window's graph (a SpacetimeCode of
+                # the rounds it covers) with the committed fold as its base
+                from .window import WindowedDecoder, spacetime_windows
+                self.wd = WindowedDecoder(spacetime_windows(self.H, R, window, commit), prior, logicals=lz, **common)
+                self.st = self.wd.final_decoder
+                Hst = self.st.H
+            else:
+                self.st = Decoder(Hst, prior, n_data=n, fold_blocks=R + 1, logicals=lz, **common)
             self.st_osd = OsdSolver(Hst, osd_method, osd_order, osd_threads) if mode == "bposd" else None
             if mode == "bprelay":
                 self.st.set_relay(**self.relay_kw)
@@ -473,7 +498,8 @@ class BatchPipeline:
     # ----------------------------------------------------------- helpers
     def decoders(self):
         """The BP decoders this pipeline launches (for the timing ring)."""
-        return [d for d in (getattr(self, k, None) for k in ("st", "fin", "ss", "det")) if d is not None]
+        decs = [d for d in (getattr(self, k, None) for k in ("st", "fin", "ss", "det")) if d is not None]
+        return decs + [d for d in (self.wd.distinct if self.wd is not None else []) if d not in decs]
 
     def sample(self, sim, B: int, seed: int, stream_id: int = 0, shot0: int = 0):
         """The device tensors run() takes, sampled from `sim` (a StorageSim of the
@@ -485,7 +511,10 @@ class BatchPipeline:
 
     def launches_per_batch(self, dec) -> int:
         """Decode calls `dec` receives per run(): the single-shot decoder runs
-        once per syndrome round, every other decoder once."""
+        once per syndrome round, a window decoder once per window it serves,
+        every other decoder once."""
+        if self.wd is not None and dec in self.wd.distinct:
+            return sum(d is dec for d in self.wd.decoders)
         return self.R if dec is getattr(self, "ss", None) else 1
 
     def _fail_host(self, readout, corr):
@@ -582,7 +611,9 @@ class BatchPipeline:
                               placement=self.relay_placement)
         return conv
 
-    def run(self, syn, readout, want_corrections: bool = False) -> BatchResult:
+    def run(self, syn, readout, want_corrections: bool = False, want_detail: bool = False) -> BatchResult:
+        """want_detail: the result's ``detail`` holds the shots' iters and status
+        as the device stages left them (host arrays)."""
         torch = _torch()
         B = syn.shape[0]
         dev = syn.device
@@ -600,21 +631,36 @@ class BatchPipeline:
         mode = self.mode
         if mode in ("bp", "bposd"):
             need_llr = mode == "bposd"
+            base = w_iters = w_status = None
+            if self.wd is not None:
+                # the non-final windows fold their committed data blocks into
+                # `base`; the final window's syndrome comes back for the stage below
+                base = torch.zeros((B, n), **u8)
+                w_iters, w_status = torch.zeros(B, **i32), torch.zeros(B, **u8)
+                osd = (dict(method=self.osd_method, order=self.osd_order, rows=self.osd_rows,
+                            threads=self.osd_threads) if need_llr else None)
+                syn = self.wd.decode_device(B, syn.clone(), base, iters=w_iters, status=w_status, osd=osd,
+                                            stop_before_final=True)
             llr = torch.empty((B, self.st.n), dtype=torch.float32 if self.st.precision == _abi.QD_F32
                               else torch.float64, device=dev) if need_llr else None
-            self.st.decode_device(B, syn=syn, readout=readout, corr=corr, llr=llr, iters=iters, status=status,
-                                  fail=fail)
+            self.st.decode_device(B, syn=syn, base=base, readout=readout, corr=corr, llr=llr, iters=iters,
+                                  status=status, fail=fail)
             rows = _osd_rows_for(self.st, self.osd_rows) if need_llr else None
             if rows:
                 self.st.osd_device(B, llr=llr, method=self.osd_method, order=self.osd_order, syn=syn, status=status,
-                                   readout=readout, corr=corr, fail=fail, rows=rows)
+                                   base=base, readout=readout, corr=corr, fail=fail, rows=rows)
             elif need_llr:
                 idx, ow = self._osd_fix(self.st, self.st_osd, syn, status, llr, B)
                 if idx is not None:
                     fold = np.zeros((idx.size, n), np.uint8)
-                    for t in range(R + 1):
+                    for t in range(self.st.fold_blocks):
                         fold ^= ow[:, t * n:(t + 1) * n]
+                    if base is not None:
+                        fold ^= base.index_select(0, torch.from_numpy(idx).to(dev)).cpu().numpy()
                     host_fix = (idx, fold)
+            if self.wd is not None:  # iterations add up; BP converged in every window or not at all
+                iters += w_iters
+                status &= (w_status | 0xFE)
         elif mode in ("bposd_hybrid", "bpssf_hybrid"):
             c1 = torch.empty((B, n), **u8)
             self.st.decode_device(B, syn=syn, corr=c1, iters=iters)
@@ -711,7 +757,9 @@ class BatchPipeline:
         return BatchResult(fail=fail_h, bp_converged=int(((status & 1).sum() if bp_conv is None else bp_conv).item()),
                            iters_sum=int(iters.to(torch.int64).sum().item()),
                            ssf_steps_sum=int(steps.to(torch.int64).sum().item()),
-                           corrections=corr_h if want_corrections else None)
+                           corrections=corr_h if want_corrections else None,
+                           detail={"iters": iters.cpu().numpy(), "status": status.cpu().numpy()} if want_detail
+                           else None)
 
 
 # ------------------------------------------------------------------ per-shot API
@@ -795,13 +843,15 @@ def run_simulation(samples, code, meas_prior, data_prior, noise_model, noise_mod
                    decoder_mode, *, seed: int = DEFAULT_SEED, stream_id: int = 0, shot0: int = 0, device: int = 0,
                    batch: int = 1 << 18, precision: str = "f64", stats: dict | None = None,
                    dem_source: str | None = None, osd_rows: str | None = None,
-                   llr_budget_bytes: int = DEFAULT_LLR_BUDGET, approximate_disjoint_errors: bool = False):
+                   llr_budget_bytes: int = DEFAULT_LLR_BUDGET, approximate_disjoint_errors: bool = False,
+                   window: int | None = None, commit: int | None = None):
     """Sample and decode `samples` shots on one GPU; returns a bool ndarray of
     logical-failure flags (reference run_simulation, _experiment.py:154-210,
     which returns a list of the same flags).  dem_source="circuit": bpd_detector
     decodes the DEM extracted from the circuit under any noise model (the
     default under every rewriter but depolarizing_noise);
-    approximate_disjoint_errors: dem.detector_error_model's, for that DEM."""
+    approximate_disjoint_errors: dem.detector_error_model's, for that DEM.
+    window, commit: BatchPipeline's (sliding-window decoding; bp and bposd)."""
     torch = _torch()
     x_steps, z_steps = _steps(code.checks)
     sim = build_storage_simulation(rounds, noise_model(**noise_model_args), code, use_x_logicals=False)
@@ -809,7 +859,8 @@ def run_simulation(samples, code, meas_prior, data_prior, noise_model, noise_mod
     dp = data_prior(x_steps, z_steps)
     pipe = BatchPipeline(code, rounds, decoder_mode, bp_osd_options, (dp, mp), device=device, precision=precision,
                          noise=noise_model(**noise_model_args), dem_source=dem_source, sim=sim, osd_rows=osd_rows,
-                         llr_budget_bytes=llr_budget_bytes, approximate_disjoint_errors=approximate_disjoint_errors)
+                         llr_budget_bytes=llr_budget_bytes, approximate_disjoint_errors=approximate_disjoint_errors,
+                         window=window, commit=commit)
     out = np.zeros(samples, dtype=bool)
     agg = {"bp_converged": 0, "iters_sum": 0, "ssf_steps_sum": 0}
     with torch.cuda.device(device):
@@ -1032,7 +1083,8 @@ HBM_PEAK_BYTES_S = 8.0e12  # MI355X HBM3E peak (MI355X_MICROARCH.md)
 def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_prior, *, gpus: int | None = None,
             devices=None, seed: int = DEFAULT_SEED, batch: int = 1 << 18, precision: str = "f64",
             checkpoint: str | None = None, dem_source: str | None = None, osd_rows: str | None = None,
-            approximate_disjoint_errors: bool = False, **kwargs):
+            approximate_disjoint_errors: bool = False, window: int | None = None, commit: int | None = None,
+            **kwargs):
     """Sweep the physical error rate (reference p_sweep, misc/p_sweep.py:17-40).
     Shots are sharded over `gpus` devices by index (shard d decodes a
     contiguous shot range); exactly `samples` shots per point.  `devices`
@@ -1058,9 +1110,19 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
     dem_source: BatchPipeline's; points decoded on the circuit's own DEM carry
     dem_sector = "circuit".  osd_rows: BatchPipeline's (where the OSD stage runs;
     the failure counts do not depend on it).  approximate_disjoint_errors:
-    dem.detector_error_model's, for the circuit's DEM."""
+    dem.detector_error_model's, for the circuit's DEM.  window, commit:
+    BatchPipeline's (sliding-window decoding of bp / bposd; commit defaults to
+    max(1, window // 2)); such points carry both as columns, and their
+    fingerprint differs from the full-graph one."""
     import pandas as pd
     torch = _torch()
+    if window is not None:
+        from .window import check_window_args
+        if kwargs["decoder_mode"] not in WINDOW_MODES:
+            raise ValueError(f"window applies to the decoder modes {WINDOW_MODES} only")
+        window, commit = check_window_args(window, commit)
+    elif commit is not None:
+        raise ValueError("commit applies to a windowed decode only (window=...)")
     done = _load_checkpoint(checkpoint)
     devs = [int(d) for d in devices] if devices else list(range(gpus or _device_count()))
     ndev = len(devs)
@@ -1075,7 +1137,8 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
         dp = data_prior(p_ph, x_steps, z_steps)
         mp = meas_prior(p_ph, x_steps, z_steps)
         fp = _config_fingerprint(code, rounds, (mode if dem_source is None else f"{mode}/dem={dem_source}") +
-                                 ("/approximate_disjoint_errors" if approximate_disjoint_errors else ""),
+                                 ("/approximate_disjoint_errors" if approximate_disjoint_errors else "") +
+                                 (f"/window={window},{commit}" if window is not None else ""),
                                  bp_osd_options, precision, seed, samples, pi, noise=(noise_model, nm_args, dp, mp))
         prev = done.get((float(p_ph), fp))
         if prev is not None:
@@ -1088,7 +1151,8 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
         def pipeline(d):
             return BatchPipeline(code, rounds, mode, bp_osd_options, (dp, mp), device=d, precision=precision,
                                  noise=nm, dem_source=dem_source, sim=sim, osd_rows=osd_rows,
-                                 approximate_disjoint_errors=approximate_disjoint_errors)
+                                 approximate_disjoint_errors=approximate_disjoint_errors, window=window,
+                                 commit=commit)
         pipes = [pipeline(d) for d in devs]
         per = math.ceil(samples / ndev)
         shards = [(i, i * per, min(samples, (i + 1) * per)) for i in range(ndev)]
@@ -1138,6 +1202,8 @@ def p_sweep(samples, p_values, noise_model, noise_model_args, meas_prior, data_p
         point["precision"] = precision
         point["point_index"] = pi
         point["config_fp"] = fp
+        if window is not None:
+            point["window"], point["commit"] = window, commit
         if pipes[0].dem_source == "circuit":
             point["dem_sector"] = "circuit"          # dem.detector_error_model of the sampled circuit
         elif mode in DETECTOR_MODES and rounds >= 2:
@@ -1195,6 +1261,11 @@ def p_sweep_main(noise_model_args, noise_model, meas_prior, data_prior):
                              "bposd_detector)")
     parser.add_argument("--checkpoint", type=str, default=None,
                         help="CSV that each finished point is appended to; finished points are skipped on restart")
+    parser.add_argument("--window", type=int, default=None,
+                        help="sliding-window decoding of bp / bposd: rounds per window (default: off, one graph over "
+                             "all rounds)")
+    parser.add_argument("--commit", type=int, default=None,
+                        help="rounds committed per window (default: max(1, window // 2))")
     parser.add_argument("--approximate_disjoint_errors", action="store_true",
                         help="circuit DEM: a PAULI_CHANNEL without an exact decomposition into independent "
                              "mechanisms contributes its arguments as independent probabilities (default: refused)")
@@ -1209,6 +1280,7 @@ def p_sweep_main(noise_model_args, noise_model, meas_prior, data_prior):
                      p_values=sweep, decoder_mode=args.decoder_mode, bp_osd_options=bp_osd_options,
                      gpus=args.gpus, devices=args.devices, seed=args.seed, batch=args.batch, precision=args.precision,
                      checkpoint=args.checkpoint, osd_rows=args.osd_rows,
-                     approximate_disjoint_errors=args.approximate_disjoint_errors)
+                     approximate_disjoint_errors=args.approximate_disjoint_errors, window=args.window,
+                     commit=args.commit)
     result.to_csv(sys.stdout)
     return result

@@ -515,6 +515,51 @@ int qd_relay_set_slots(qd_graph* g, int64_t slots);
 int qd_relay_info(const qd_graph* g, int32_t precision, int32_t placement, int64_t out[4]);
 int64_t qd_relay_kernel_names(char* buf, int64_t cap);
 
+/* ---- sliding-window decoding: the step between two windows ----------------
+ * (csrc/qdec_window.hip; no reference counterpart: the reference
+ * left it as a stub, spacetime_code.py:95-96).  A layered graph is decoded
+ * window by window; a qd_window is one boundary: what the window's committed
+ * columns do to the rows of the full syndrome that later windows read (the
+ * carry table), what they add to an accumulator (the fold of a spacetime code,
+ * the observables of a detector error model), and which rows of the full
+ * syndrome the next window takes.
+ *
+ * Tables (copied): carry row i is global row carry_rows[i] (strictly ascending,
+ * inside [0, m_total)) and reads the window-local columns carry_cols[
+ * carry_ptr[i] .. carry_ptr[i + 1]); accumulator row i reads acc_cols[
+ * acc_ptr[i] .. acc_ptr[i + 1]).  A column that is not committed is simply not
+ * listed.  Refusals, before anything is copied or enqueued: -26 a null handle,
+ * output or array, a negative size, n_w < 1 or above 2^19; -25 row0 + m_next >
+ * m_total (or either negative); -24 a pointer array that does not start at 0 or
+ * decreases; -22 carry rows unsorted, repeated or out of range; -23 a column
+ * outside [0, n_w); -15 device ordinal.  qd_window_create_host validates the
+ * same way and makes no HIP call (its handle refuses to run, -16).
+ *
+ * qd_window_advance_device, per shot b (all buffers uint8, one byte per bit;
+ * bit 0 of an x byte counts), enqueued on `stream`:
+ *   syn_full[b][carry_rows[i]] ^= xor_{c in carry row i} x[b][c]
+ *   acc_out[b][i]              ^= xor_{c in acc row i} x[b][c]      (acc_out may be NULL)
+ *   syn_next[b][i]              = syn_full[b][row0 + i], after the carry (syn_next may be NULL)
+ * x = NULL: no carry and no accumulate, only the copy (it stages the first
+ * window).  syn_full [B][m_total] is updated in place -- a column that spans
+ * more layers than a window commits carries into windows after the next one --
+ * and no other byte of it is written.  -28 B < 0 or a NULL syn_full that would
+ * be read.  B = 0 returns 0 and writes nothing.
+ * qd_window_set_blocks: workgroups of later launches (0 = the default, 8 per
+ * compute unit; a launch uses at most B; -29 outside 0 .. 2^20).  Results do
+ * not depend on it. */
+typedef struct qd_window qd_window;
+int qd_window_create(int32_t device, int32_t n_w, int32_t m_total, int32_t n_carry, const int32_t* carry_rows,
+                     const int32_t* carry_ptr, const int32_t* carry_cols, int32_t k_acc, const int32_t* acc_ptr,
+                     const int32_t* acc_cols, int32_t row0, int32_t m_next, qd_window** out);
+int qd_window_create_host(int32_t n_w, int32_t m_total, int32_t n_carry, const int32_t* carry_rows,
+                          const int32_t* carry_ptr, const int32_t* carry_cols, int32_t k_acc, const int32_t* acc_ptr,
+                          const int32_t* acc_cols, int32_t row0, int32_t m_next, qd_window** out);
+int qd_window_advance_device(qd_window* w, int64_t B, const uint8_t* x, uint8_t* syn_full, uint8_t* acc_out,
+                             uint8_t* syn_next, void* stream);
+int qd_window_set_blocks(qd_window* w, int64_t blocks);
+int qd_window_destroy(qd_window* w);
+
 /* Kernel timing for measurement: with capacity > 0, the next `capacity` decode
  * calls record HIP events on their launch stream immediately before the BP kernel,
  * after it and after the SSF kernel.  qd_graph_read_timing returns the per-call
