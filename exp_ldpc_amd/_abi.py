@@ -141,6 +141,8 @@ SIGNATURES = {
     "qd_graph_plan": (_i32, [_p, C.POINTER(QdParams), _i64, _u32, _p]),
     "qd_graph_plan_names": (_i32, [_p, C.POINTER(QdParams), _i64, _u32, C.c_char_p, _i32, C.c_char_p, _i32,
                                    C.c_char_p, _i32]),
+    "qd_graph_plan_entries": (_i32, [_p, C.POINTER(QdParams), _i64, _u32, C.c_char_p, _i32, C.c_char_p, _i32,
+                                     C.c_char_p, _i32]),
     "qd_kernel_table_names": (_i64, [C.c_char_p, _i64]),
     "qd_graph_it1_tables_copy": (_i32, [_p, _i32, _p, _p, C.POINTER(_i32)]),
     "qd_graph_ms_state0_copy": (_i32, [_p, _i32, _p, _p, C.POINTER(_i32)]),

@@ -1218,6 +1218,17 @@ int qd_graph_plan_names(const qd_graph* G, const qd_params* p, int64_t B, uint32
     });
 }
 
+int qd_graph_plan_entries(const qd_graph* G, const qd_params* p, int64_t B, uint32_t present, char* bp, int32_t bp_len,
+                          char* ssf, int32_t ssf_len, char* pre, int32_t pre_len) {
+    return guarded([&] {
+        const DecodePlan plan = plan_of(G, p, B, present);
+        auto entry_name = [](const KernelEntry* e) { return e ? e->name.c_str() : ""; };
+        put_name(entry_name(plan.bp_k), bp, bp_len);
+        put_name(entry_name(plan.fin_k), ssf, ssf_len);
+        put_name(entry_name(plan.pre_k), pre, pre_len);
+    });
+}
+
 int64_t qd_kernel_table_names(char* buf, int64_t cap) {
     int64_t len = 0;
     const int e = guarded([&] {

@@ -499,16 +499,30 @@ class Decoder:
         return bp.value.decode(), ssf.value.decode(), pre.value.decode()
 
     def planned_kernels(self, B: int, *, present=("syn", "readout", "fail"), aligned: bool = True,
-                        ssf: bool | None = None, packed: bool = False) -> tuple[str, str, str]:
+                        ssf: bool | None = None, packed: bool = False, syn_flags: int = 0) -> tuple[str, str, str]:
         """What last_kernels() returns after a decode of B shots passing the
         optional buffers named in `present` (syn, base, readout, x, corr, llr,
         fail), by the launch plan alone (qd_graph_plan_names): no launch."""
         bits = {"syn": 1, "base": 2, "readout": 4, "x": 8, "corr": 16, "llr": 32, "fail": 64}
         mask = sum(bits[name] for name in present) | (128 if aligned else 0)
-        prm = self._params(QD_INPUT_PACKED if packed else 0, ssf)
+        prm = self._params(int(syn_flags) | (QD_INPUT_PACKED if packed else 0), ssf)
         bp, fin, pre = (C.create_string_buffer(512) for _ in range(3))
         _abi.check(self._lib.qd_graph_plan_names(self._handle, C.byref(prm), int(B), mask, bp, 512, fin, 512, pre, 512),
                    "qd_graph_plan_names")
+        return bp.value.decode(), fin.value.decode(), pre.value.decode()
+
+    def planned_entries(self, B: int, *, present=("syn", "readout", "fail"), aligned: bool = True,
+                        ssf: bool | None = None, packed: bool = False, syn_flags: int = 0) -> tuple[str, str, str]:
+        """The kernel-table entries the launch plan of that decode holds (BP,
+        SSF, pre-pass; qd_graph_plan_entries): planned_kernels, with the stages
+        last_kernels() does not report (bp_block_kernel, the workgroup SSF
+        kernels) under their own names.  No launch."""
+        bits = {"syn": 1, "base": 2, "readout": 4, "x": 8, "corr": 16, "llr": 32, "fail": 64}
+        mask = sum(bits[name] for name in present) | (128 if aligned else 0)
+        prm = self._params(int(syn_flags) | (QD_INPUT_PACKED if packed else 0), ssf)
+        bp, fin, pre = (C.create_string_buffer(512) for _ in range(3))
+        _abi.check(self._lib.qd_graph_plan_entries(self._handle, C.byref(prm), int(B), mask, bp, 512, fin, 512, pre,
+                                                   512), "qd_graph_plan_entries")
         return bp.value.decode(), fin.value.decode(), pre.value.decode()
 
     def close(self) -> None:

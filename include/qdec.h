@@ -722,6 +722,13 @@ int qd_graph_plan(const qd_graph* g, const qd_params* p, int64_t B, uint32_t pre
  * counterpart. */
 int qd_graph_plan_names(const qd_graph* g, const qd_params* p, int64_t B, uint32_t present, char* bp,
                         int32_t bp_len, char* ssf, int32_t ssf_len, char* pre, int32_t pre_len);
+/* The same plan's entries whether or not qd_graph_last_kernels records them:
+ * as qd_graph_plan_names, except that a stage whose entry is not reported after
+ * a launch (bp_block_kernel, the workgroup SSF kernels) is written under the name
+ * qd_kernel_table_names lists it by ("" only for a stage without an entry).  No
+ * HIP call; also on host-only graphs.  No reference counterpart. */
+int qd_graph_plan_entries(const qd_graph* g, const qd_params* p, int64_t B, uint32_t present, char* bp,
+                          int32_t bp_len, char* ssf, int32_t ssf_len, char* pre, int32_t pre_len);
 /* Every instantiation the library builds for the decode kernel families: the
  * names of all entries of the kernel tables the plan picks from (wave graphs
  * first, then workgroup graphs; table order), each followed by '\n', spelled as
