@@ -98,8 +98,9 @@ void ws_drain(qd_graph* G) {
 }
 
 // Attach the queue scratch (capacity >= B shots) when the plan asks for the SSF
-// queue or the compact shot lists; one buffer holds both (queue_layout).
-void attach_queue(qd_graph* G, const DecodePlan& plan, DecodeArgs& a) {
+// queue or the compact shot lists; one buffer holds both (queue_layout).  s is
+// the stream the decode's kernels go to.
+void attach_queue(qd_graph* G, const DecodePlan& plan, DecodeArgs& a, hipStream_t s) {
     const DevGraph& g = G->dg;
     if (a.B <= 0 || (!plan.need_queue && !plan.need_lists)) return;
     if ((size_t)a.B > G->qws.cap)  // launches still in flight may use the old queue
@@ -116,11 +117,14 @@ void attach_queue(qd_graph* G, const DecodePlan& plan, DecodeArgs& a) {
         a.cmp = reinterpret_cast<uint64_t*>(base + L.cmp);
         a.cmp_cap = L.cmp_cap;
         // double-buffered counters (zeroed once here, then by each triage for
-        // the next decode): no memset launch per decode
+        // the next decode): no memset launch per decode.  Zeroed on the decode's
+        // own stream: the handle's stream is non-blocking, so a memset on the
+        // null stream is not ordered before the triage, which then adds to
+        // whatever the allocation held and writes its list entries from there
         const size_t set = (size_t)kCmpLists * kCmpSegs * 128;
         if (!G->cmpc) {
             hip_check(hipMalloc(&G->cmpc, 2 * set), "hipMalloc list counters");
-            hip_check(hipMemset(G->cmpc, 0, 2 * set), "hipMemset list counters");
+            hip_check(hipMemsetAsync(G->cmpc, 0, 2 * set, s), "hipMemsetAsync list counters");
             G->cmp_par = 0;
         }
         auto* c = static_cast<uint8_t*>(G->cmpc);
@@ -323,7 +327,7 @@ DecodeArgs make_args(const qd_graph* g, const qd_params* p, int64_t B, const uin
 void enqueue_decode(qd_graph* G, const qd_params* p, DecodeArgs& a, hipStream_t s, bool allow_split) {
     const DecodePlan plan = plan_decode(G->dg, p->method, p->precision, a);
     check_plan(plan);
-    attach_queue(G, plan, a);
+    attach_queue(G, plan, a, s);
     attach_unpack(G, plan, a);
     attach_timing(G, a);
     size_t sb = 0;

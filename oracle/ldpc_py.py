@@ -95,7 +95,9 @@ def _bp_decode(H, probs, syndrome, *, method, max_iter, ms_scaling):
                     temp += c2b[e]
         else:
             for i in range(m):
-                temp = (-1.0) ** s[i]
+                # a numpy scalar, as the docstring promises: on a check of degree 1 with syndrome 1 the
+                # division below is by zero, which gives inf as in C where a Python float raises
+                temp = np.float64((-1.0) ** s[i])
                 for e in g.rows[i]:
                     c2b[e] = temp
                     temp *= 2 / (1 + b2c[e]) - 1
