@@ -29,6 +29,7 @@ QD_INPUT_PACKED = 16  # bit-packed input rows (include/qdec.h)
 QD_ST_BP_CONVERGED, QD_ST_SATISFIED = 1, 2
 QD_OSD_ONCHIP, QD_OSD_HBM, QD_OSD_AUTO = 0, 1, 2  # where the device OSD keeps its rows
 QD_RELAY_LDS, QD_RELAY_HBM, QD_RELAY_AUTO = 0, 1, 2  # where the relay stage keeps its messages
+QD_LAYERED_LDS, QD_LAYERED_HBM, QD_LAYERED_AUTO = 0, 1, 2  # where layered BP keeps its beliefs
 
 
 class QdParams(C.Structure):
@@ -52,6 +53,14 @@ class QdRelayParams(C.Structure):
         ("num_sets", C.c_int32),
         ("set_max_iter", C.c_int32),
         ("stop_nconv", C.c_int32),
+    ]
+
+
+class QdLayeredParams(C.Structure):
+    _fields_ = [
+        ("max_iter", C.c_int32),
+        ("ms_scaling", C.c_double),
+        ("clip", C.c_double),
     ]
 
 
@@ -128,6 +137,13 @@ SIGNATURES = {
     "qd_relay_set_slots": (_i32, [_p, _i64]),
     "qd_relay_info": (_i32, [_p, _i32, _i32, _p]),
     "qd_relay_kernel_names": (_i64, [C.c_char_p, _i64]),
+    "qd_layered_batch_device": (_i32, [_p, C.POINTER(QdLayeredParams), _i32, _i64, _p, _i32, _p, _p, _p, _p, _p, _p,
+                                       _p, _p, _i32, _p]),
+    "qd_layered_batch": (_i32, [_p, C.POINTER(QdLayeredParams), _i32, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p,
+                                _i32]),
+    "qd_layered_set_slots": (_i32, [_p, _i64]),
+    "qd_layered_info": (_i32, [_p, _i32, _i32, _p]),
+    "qd_layered_kernel_names": (_i64, [C.c_char_p, _i64]),
     "qd_window_create": (_i32, [_i32, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _p, _i32, _i32, C.POINTER(_p)]),
     "qd_window_create_host": (_i32, [_i32, _i32, _i32, _p, _p, _p, _i32, _p, _p, _i32, _i32, C.POINTER(_p)]),
     "qd_window_advance_device": (_i32, [_p, _i64, _p, _p, _p, _p, _p]),

@@ -23,7 +23,8 @@ LIB = os.path.join(HERE, "libqdec_hip.so")
 SOURCES = ["qdec_osd.hip", "qdec_ms_rvx.hip", "qdec_bp.hip", "qdec_ms_rv4.hip", "qdec_bp_block.hip",
            "qdec_bp_group.hip", "qdec_ms_triage.hip", "qdec_ms_lds64.hip", "qdec_ms_lds.hip", "qdec_tables.cpp",
            "qdec_launch_wave.hip", "qdec_launch_block.hip", "qdec_abi.cpp", "qdec_osd.cpp", "qdec_hgp.cpp",
-           "qdec_abi_circuit.cpp", "qdec_sample.hip", "qdec_frame.hip", "qdec_osd_hbm.hip", "qdec_relay.hip", "qdec_circuit.cpp",
+           "qdec_abi_circuit.cpp", "qdec_sample.hip", "qdec_frame.hip", "qdec_osd_hbm.hip", "qdec_relay.hip", "qdec_layered.hip",
+           "qdec_circuit.cpp",
            "qdec_gf2.cpp", "qdec_window.hip", "qdec_abi_window.cpp", "qdec_window.cpp"]
 # device source compiled at run time (hipRTC, per hypergraph-product code): embedded
 # into the library as a string literal (build/gen/qdec_hgp_src.inc)

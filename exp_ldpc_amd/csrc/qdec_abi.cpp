@@ -71,6 +71,11 @@ struct qd_graph : HostGraph {
     RelayTables relay_t{};
     ChainedSlots relay_ws;
     void* relay_ctr = nullptr;
+    // layered BP (qd_layered_batch*): the slot scratch of the HBM placement, whose
+    // chain orders the launches of both placements (slots_cfg:
+    // qd_layered_set_slots), and the launches' shot counter
+    ChainedSlots layered_ws;
+    void* layered_ctr = nullptr;
     // kernels the last decode on this handle launched (qd_graph_last_kernels)
     std::string last_bp, last_ssf, last_pre;
     // qd_graph_create_host: tables only, no device, no stream; decodes refuse it
@@ -215,6 +220,11 @@ void build_relay(qd_graph* G) {
 int64_t relay_lds_grid(const qd_graph* G, const RelayLayout& L) {
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kRelayLdsPerCu, (int64_t)kRelayLdsMax / L.lds_bytes(false)));
     return G->relay_ws.slots_cfg > 0 ? G->relay_ws.slots_cfg : (int64_t)G->num_cus * per_cu;
+}
+
+void check_layered_placement(int32_t placement) {
+    if (placement != QD_LAYERED_LDS && placement != QD_LAYERED_HBM && placement != QD_LAYERED_AUTO)
+        throw Fail(-68, "unknown layered placement (0 LDS, 1 HBM, 2 auto)");
 }
 
 void note_kernels(qd_graph* G) {
@@ -580,6 +590,8 @@ int qd_graph_destroy(qd_graph* g) {
         g->osd_ws.destroy();  // an HBM OSD launch may still use its slots
         g->relay_ws.destroy();
         if (g->relay_ctr) (void)hipFree(g->relay_ctr);
+        g->layered_ws.destroy();
+        if (g->layered_ctr) (void)hipFree(g->layered_ctr);
         if (g->cmpc) (void)hipFree(g->cmpc);
         if (g->ctl) (void)hipFree(g->ctl);
         hgp_plan_destroy(g->hgp);
@@ -619,6 +631,7 @@ int qd_graph_set_priors(qd_graph* G, const double* probs) {
     return guarded([&] {
         check_graph(G);
         set_device(G);
+        if (!G->host_only) G->layered_ws.chain.drain();  // a layered launch may still read the old priors
         set_priors(G, probs);  // on a throw the previous tables and flags stand
         G->has_priors = G->bp_priors;
         G->has_thr = true;
@@ -994,6 +1007,138 @@ int qd_relay_batch(qd_graph* G, int32_t precision, int64_t B, const uint8_t* syn
                           st.dev<uint8_t>(3), st.dev<uint8_t>(4), st.dev(5), st.dev<int32_t>(6), st.dev<int32_t>(7),
                           st.dev<uint8_t>(8), st.dev<uint8_t>(9), nullptr};
         enqueue_relay(G, precision, a, L, kind, s);
+        st.finish(3, s);
+    });
+}
+
+int qd_layered_set_slots(qd_graph* G, int64_t slots) {
+    return guarded([&] {
+        check_graph(G);
+        if (slots < 0 || slots > kLayeredMaxSlots) throw Fail(-49, "layered slots must be 0 (default) .. 2^20");
+        G->layered_ws.slots_cfg = slots;
+    });
+}
+
+int qd_layered_info(const qd_graph* G, int32_t precision, int32_t placement, int64_t out[4]) {
+    return guarded([&] {
+        check_graph(G);
+        if (precision != QD_F32 && precision != QD_F64) throw Fail(-4, "unknown precision");
+        check_layered_placement(placement);
+        if (!out) throw Fail(-49, "null output");
+        const LayeredLayout L(G->dg, precision == QD_F32 ? 4 : 8);
+        const int kind = layered_place(L, placement);
+        if (kind < 0) throw Fail(-111, "graph too large for this layered placement (LDS above 160 KiB)");
+        out[0] = kind;
+        out[1] = L.lds_bytes(kind == QD_LAYERED_HBM);
+        out[2] = kind == QD_LAYERED_HBM ? L.slot_bytes : 0;
+        out[3] = G->layered_ws.slots_last;
+    });
+}
+
+int64_t qd_layered_kernel_names(char* buf, int64_t cap) {
+    int64_t len = 0;
+    const int e = guarded([&] {
+        std::string s;
+        append_layered_kernel_names(s);
+        len = put_name(s, buf, cap);
+    });
+    return e ? e : len;
+}
+
+// the checks both layered entry points share, in the order qdec.h lists them
+// (relay's order); false: B = 0, nothing to do
+static bool check_layered_call(const qd_graph* G, const qd_layered_params* prm, int32_t precision, int64_t B,
+                               const uint8_t* syn, int32_t syn_flags, const uint8_t* base, const uint8_t* readout,
+                               const uint8_t* fail, int32_t placement, LayeredLayout* L, int* kind) {
+    static_assert(sizeof(qd_layered_params) == sizeof(LayeredParams), "qd_layered_params and LayeredParams");
+    check_graph(G);
+    if (precision != QD_F32 && precision != QD_F64) throw Fail(-4, "unknown precision");
+    if (B < 0) throw Fail(-8, "negative batch");
+    check_layered_placement(placement);
+    layered_check_params(reinterpret_cast<const LayeredParams*>(prm));
+    if (syn_flags & QD_INPUT_PACKED) throw Fail(-69, "layered BP takes byte rows (QD_INPUT_PACKED refused)");
+    if (syn_flags & ~3) throw Fail(-69, "unknown syn_flags");
+    if (fail && readout && G->dg.k > 0 && (G->dg.k > 256 || !G->dg.lz))
+        throw Fail(-69, "fused failure check after layered BP supports <= 256 logicals");
+    if (!G->has_priors && G->has_thr)
+        throw Fail(-51, "the graph's priors hold a 0 or a 1: layered BP needs probabilities inside (0, 1)");
+    if (!G->has_priors) throw Fail(-5, "priors not set (qd_graph_set_priors)");
+    if (B == 0) return false;
+    if (!syn && !(syn_flags && (base || readout))) throw Fail(-7, "no syndrome source");
+    *L = LayeredLayout(G->dg, precision == QD_F32 ? 4 : 8);
+    *kind = layered_place(*L, placement);
+    if (*kind < 0) throw Fail(-111, "graph too large for this layered placement (LDS above 160 KiB)");
+    if (G->host_only) throw Fail(-16, "host-only graph (qd_graph_create_host): no device to run layered BP on");
+    return true;
+}
+
+static void enqueue_layered(qd_graph* G, int32_t precision, const LayeredArgs& args, const LayeredLayout& L, int kind,
+                            hipStream_t s) {
+    LayeredArgs a = args;
+    int64_t grid;
+    void* scr = nullptr;
+    if (kind == QD_LAYERED_HBM) {
+        grid = G->layered_ws.acquire(layered_slot_rule((size_t)L.slot_bytes, (int64_t)G->num_cus * kLayeredSlotsPerCu),
+                                     a.B, s);
+        scr = G->layered_ws.ptr;
+    } else {  // no slots, but the shot counter is the handle's: the same chain
+        G->layered_ws.chain.acquire(s);
+        const int64_t cfg = G->layered_ws.slots_cfg;
+        grid = std::min(cfg > 0 ? cfg : (int64_t)G->num_cus * layered_lds_per_cu(L), a.B);
+    }
+    if (!G->layered_ctr) hip_check(hipMalloc(&G->layered_ctr, 256), "hipMalloc layered counter");
+    a.work_ctr = static_cast<unsigned long long*>(G->layered_ctr);
+    hip_check(hipMemsetAsync(a.work_ctr, 0, sizeof(unsigned long long), s), "hipMemsetAsync layered counter");
+    const int rc = launch_layered(G->dg, precision, a, L, scr, grid, s);
+    G->layered_ws.release(grid, s);
+    if (rc != 0) throw Fail(-105, std::string("layered launch failed: ") + hipGetErrorString((hipError_t)rc));
+}
+
+int qd_layered_batch_device(qd_graph* G, const qd_layered_params* prm, int32_t precision, int64_t B,
+                            const uint8_t* syn, int32_t syn_flags, const uint8_t* base, const uint8_t* readout,
+                            uint8_t* x_out, uint8_t* corr_out, void* llr_out, int32_t* iters, uint8_t* status,
+                            uint8_t* fail, int32_t placement, void* stream) {
+    return guarded([&] {
+        LayeredLayout L;
+        int kind = 0;
+        if (!check_layered_call(G, prm, precision, B, syn, syn_flags, base, readout, fail, placement, &L, &kind))
+            return;
+        set_device(G);
+        const LayeredArgs a{B, prm->max_iter, syn_flags, prm->ms_scaling, prm->clip, syn, base, readout, x_out,
+                            corr_out, llr_out, iters, status, fail, nullptr};
+        enqueue_layered(G, precision, a, L, kind, (hipStream_t)stream);
+    });
+}
+
+int qd_layered_batch(qd_graph* G, const qd_layered_params* prm, int32_t precision, int64_t B, const uint8_t* syn,
+                     int32_t syn_flags, const uint8_t* base, const uint8_t* readout, uint8_t* x_out,
+                     uint8_t* corr_out, void* llr_out, int32_t* iters, uint8_t* status, uint8_t* fail,
+                     int32_t placement) {
+    return guarded([&] {
+        LayeredLayout L;
+        int kind = 0;
+        if (!check_layered_call(G, prm, precision, B, syn, syn_flags, base, readout, fail, placement, &L, &kind))
+            return;
+        set_device(G);
+        const DevGraph& g = G->dg;
+        const size_t tsz = precision == QD_F32 ? 4 : 8;
+        HostStage st;  // regions 0-2 the inputs, 3-8 every output passed
+        st.add(syn, (size_t)B * g.m, "layered input");
+        st.add(base, (size_t)B * g.n_data, "layered input");
+        st.add(readout, (size_t)B * g.n_data, "layered input");
+        st.add(x_out, (size_t)B * g.n, "layered output");
+        st.add(corr_out, (size_t)B * g.n_data, "layered output");
+        st.add(llr_out, (size_t)B * g.n * tsz, "layered output");
+        st.add(iters, (size_t)B * 4, "layered output");
+        st.add(status, (size_t)B, "layered output");
+        st.add(fail, (size_t)B, "layered output");
+        st.place(G->ws);
+        hipStream_t s = G->stream;
+        st.copy(0, 3, true, s);
+        const LayeredArgs a{B, prm->max_iter, syn_flags, prm->ms_scaling, prm->clip, st.dev<uint8_t>(0),
+                            st.dev<uint8_t>(1), st.dev<uint8_t>(2), st.dev<uint8_t>(3), st.dev<uint8_t>(4), st.dev(5),
+                            st.dev<int32_t>(6), st.dev<uint8_t>(7), st.dev<uint8_t>(8), nullptr};
+        enqueue_layered(G, precision, a, L, kind, s);
         st.finish(3, s);
     });
 }

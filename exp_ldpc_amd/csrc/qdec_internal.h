@@ -12,6 +12,7 @@
 
 #include "qdec_circuit.h"
 #include "qdec_graph.h"
+#include "qdec_layered.h"
 #include "qdec_relay.h"
 #include "qdec_window.h"
 
@@ -207,6 +208,16 @@ const KernelTable& relay_table();
 void append_relay_kernel_names(std::string& out);
 int launch_relay(const DevGraph& g, int precision, const RelayArgs& a, const RelayTables& t, const RelayLayout& L,
                  void* scratch, int64_t grid, hipStream_t stream);
+
+// layered_wave_kernel (qdec_layered.hip; arguments and layouts: qdec_layered.h).
+// A table of its own as well (layered_table: precision x placement).
+// launch_layered enqueues `grid` one-wave workgroups; with the beliefs in HBM
+// `scratch` holds `grid` slots of L.slot_bytes, else it is null.
+void add_layered_kernels(KernelTable& t);
+const KernelTable& layered_table();
+void append_layered_kernel_names(std::string& out);
+int launch_layered(const DevGraph& g, int precision, const LayeredArgs& a, const LayeredLayout& L, void* scratch,
+                   int64_t grid, hipStream_t stream);
 
 // window_advance_kernel (qdec_window.hip; tables and arguments: qdec_window.h):
 // `grid` workgroups take the B shots grid-strided.  Returns hipError_t as int.

@@ -34,6 +34,8 @@ SSF_KERNELS = {"auto": 0, "scan": 1, "scan_gather": 2, "scan_nosplit": 3}  # val
 # route pipelines that build their decoders internally through one kernel path)
 DEFAULT_OPTIONS: dict = {}
 
+_DEFAULT_WANT = ("x", "corr", "iters", "status", "ssf_steps", "fail")
+
 _PS_NAMES = {"ps", "product_sum", "prod_sum", "0", "prod sum", "product sum"}
 _MS_NAMES = {"ms", "minimum_sum", "min_sum", "1", "minimum sum", "min sum",
              "msl", "minimum_sum_log", "ms_log", "min_sum_log", "3", "minimum sum_log", "minimum sum log"}
@@ -80,7 +82,23 @@ def as_csr01(H) -> sp.csr_matrix:
 class Decoder:
     def __init__(self, H, channel_probs, *, method="ms", precision="f32", max_iter: int = 0,
                  ms_scaling: float = 0.0, flip_sets=None, ssf: bool | None = None, ssf_max_steps: int = 0,
-                 logicals=None, n_data: int | None = None, fold_blocks: int = 1, device: int = 0):
+                 logicals=None, n_data: int | None = None, fold_blocks: int = 1, device: int = 0,
+                 schedule: str = "flooding", layered_clip: float = 2.0 ** 64, layered_placement: str = "auto"):
+        """schedule: "flooding" (every check, then every variable: the decode
+        families of DESIGN 3) or "layered" (check-serial min-sum, DESIGN 3.6f:
+        decode / decode_device call qd_layered_batch / _device with this
+        decoder's max_iter, ms_scaling and precision, the beliefs clamped to
+        +-layered_clip and kept where layered_placement says: "lds", "hbm" or
+        "auto").  The layered schedule is min-sum on byte rows without SSF."""
+        self.schedule = parse_schedule(schedule)
+        self.layered_clip = float(layered_clip)
+        self.layered_placement = layered_placement
+        layered_placement_code(layered_placement)
+        if self.schedule == "layered":  # refused before a handle exists
+            if parse_bp_method(method) != _abi.QD_MIN_SUM:
+                raise ValueError("schedule='layered' is min-sum only (bp_method 'ms')")
+            if ssf or flip_sets is not None:
+                raise ValueError("schedule='layered' does not run SSF: pass neither ssf=True nor flip sets")
         self._lib = _abi.load()
         H = as_csr01(H)
         self.H = H
@@ -117,6 +135,8 @@ class Decoder:
         _abi.check(self._lib.qd_graph_set_priors(self._handle, _abi.ptr(p)), "qd_graph_set_priors")
 
     def set_flip_sets(self, generators) -> None:
+        if self.schedule == "layered":
+            raise ValueError("schedule='layered' does not run SSF: pass neither ssf=True nor flip sets")
         G = as_csr01(generators)
         if G.shape[1] != self.n:
             raise ValueError("flip-set generators must have one column per decoding column")
@@ -156,12 +176,29 @@ class Decoder:
         return np.float32 if self.precision == _abi.QD_F32 else np.float64
 
     # ------------------------------------------------------------ decoding
+    def _layered_params(self) -> _abi.QdLayeredParams:
+        return _abi.QdLayeredParams(self.max_iter if self.max_iter > 0 else self.n, self.ms_scaling, self.layered_clip)
+
+    def _layered_refuse(self, ssf, packed, ssf_steps) -> None:
+        if ssf:
+            raise ValueError("schedule='layered' does not run SSF")
+        if packed:
+            raise ValueError("schedule='layered' takes byte rows: packed=True is not supported")
+        if ssf_steps:
+            raise ValueError("schedule='layered' has no ssf_steps output")
+
     def decode(self, syn=None, *, base=None, readout=None, syn_flags: int = 0, ssf: bool | None = None,
-               want=("x", "corr", "iters", "status", "ssf_steps", "fail"), packed: bool = False) -> dict:
+               want=_DEFAULT_WANT, packed: bool = False) -> dict:
         """Decode B shots from host arrays; returns numpy arrays for `want`
-        (any of x, corr, llr, iters, status, ssf_steps, fail).  packed=True:
-        syn / base / readout are bit-packed rows (uint64 words, pack_rows;
-        QD_INPUT_PACKED)."""
+        (any of x, corr, llr, iters, status, ssf_steps, fail; by default all but
+        llr, and under schedule="layered" all but llr and ssf_steps).
+        packed=True: syn / base / readout are bit-packed rows (uint64 words,
+        pack_rows; QD_INPUT_PACKED)."""
+        layered = self.schedule == "layered"
+        if want is _DEFAULT_WANT and layered:
+            want = tuple(w for w in want if w != "ssf_steps")
+        if layered:
+            self._layered_refuse(ssf, packed, "ssf_steps" in want)
         def u8(a, cols):
             if a is None:
                 return None
@@ -193,8 +230,16 @@ class Decoder:
             out["ssf_steps"] = np.empty(B, np.int32)
         if "fail" in want:
             out["fail"] = np.empty(B, np.uint8)
-        prm = self._params(syn_flags, ssf)
         g = out.get
+        if layered:
+            prm = self._layered_params()
+            _abi.check(self._lib.qd_layered_batch(
+                self._handle, C.byref(prm), self.precision, B, _abi.ptr(syn), int(syn_flags), _abi.ptr(base),
+                _abi.ptr(readout), _abi.ptr(g("x")), _abi.ptr(g("corr")), _abi.ptr(g("llr")), _abi.ptr(g("iters")),
+                _abi.ptr(g("status")), _abi.ptr(g("fail")), layered_placement_code(self.layered_placement)),
+                "qd_layered_batch")
+            return out
+        prm = self._params(syn_flags, ssf)
         _abi.check(self._lib.qd_decode_batch(
             self._handle, C.byref(prm), B, _abi.ptr(syn), _abi.ptr(base), _abi.ptr(readout),
             _abi.ptr(g("x")), _abi.ptr(g("corr")), _abi.ptr(g("llr")), _abi.ptr(g("iters")),
@@ -223,6 +268,15 @@ class Decoder:
                                   ("iters", iters, "int32", 1), ("status", status, "uint8", 1),
                                   ("ssf_steps", ssf_steps, "int32", 1), ("fail", fail, "uint8", 1)):
             self._check_device_buffer(name, t, dt, B * cols)
+        if self.schedule == "layered":
+            self._layered_refuse(ssf, packed, ssf_steps is not None)
+            prm = self._layered_params()
+            _abi.check(self._lib.qd_layered_batch_device(
+                self._handle, C.byref(prm), self.precision, B, _abi.ptr(syn), int(syn_flags), _abi.ptr(base),
+                _abi.ptr(readout), _abi.ptr(x), _abi.ptr(corr), _abi.ptr(llr), _abi.ptr(iters), _abi.ptr(status),
+                _abi.ptr(fail), layered_placement_code(self.layered_placement), C.c_void_p(stream)),
+                "qd_layered_batch_device")
+            return
         prm = self._params(syn_flags, ssf)
         _abi.check(self._lib.qd_decode_batch_device(
             self._handle, C.byref(prm), int(B), _abi.ptr(syn), _abi.ptr(base), _abi.ptr(readout), _abi.ptr(x),
@@ -421,6 +475,23 @@ class Decoder:
         launch) of qd_relay_info; kind 0 = messages in LDS, 1 = in HBM."""
         return relay_info(self._handle, self.precision, placement)
 
+    # ------------------------------------------------------------ layered BP
+    def set_layered_slots(self, slots: int = 0) -> None:
+        """Workgroups of later layered launches in both placements
+        (qd_layered_set_slots); 0 = the default.  Results do not depend on it."""
+        _abi.check(self._lib.qd_layered_set_slots(self._handle, int(slots)), "qd_layered_set_slots")
+
+    def layered_info(self, placement: str | None = None) -> tuple[int, int, int, int]:
+        """(kind, dynamic LDS bytes, bytes per slot, workgroups of the last
+        launch) of qd_layered_info; kind 0 = beliefs in LDS, 1 = in HBM."""
+        return layered_info(self._handle, self.precision, self.layered_placement if placement is None else placement)
+
+    @staticmethod
+    def layered_kernel_names() -> list[str]:
+        """Every instantiation of the layered kernel the library builds
+        (qd_layered_kernel_names), in rocprofv3's spelling."""
+        return layered_kernel_names()
+
     def set_wave_occupancy(self, waves_per_cu: int = 0) -> None:
         """Waves per CU of the wave BP kernels (qd_graph_set_wave_occupancy):
         0 = the default; more for decodes that run concurrently on several
@@ -558,6 +629,47 @@ def relay_placement(placement) -> int:
     if placement not in RELAY_PLACEMENTS:
         raise ValueError(f"placement must be one of {sorted(RELAY_PLACEMENTS)}, got {placement!r}")
     return RELAY_PLACEMENTS[placement]
+
+
+SCHEDULES = {"flooding": "flooding", "parallel": "flooding", "layered": "layered"}
+
+
+def parse_schedule(schedule) -> str:
+    """schedule name -> "flooding" | "layered" ("parallel" is ldpc v2's name of
+    flooding; its "serial" is variable-serial, another algorithm, and is not
+    accepted)."""
+    key = str(schedule).strip().lower()
+    if key not in SCHEDULES:
+        raise ValueError(f"schedule must be one of {sorted(SCHEDULES)}, got {schedule!r}")
+    return SCHEDULES[key]
+
+
+LAYERED_PLACEMENTS = {"lds": _abi.QD_LAYERED_LDS, "hbm": _abi.QD_LAYERED_HBM, "auto": _abi.QD_LAYERED_AUTO}
+
+
+def layered_placement_code(placement) -> int:
+    """placement ("lds" | "hbm" | "auto") -> QD_LAYERED_*."""
+    if placement not in LAYERED_PLACEMENTS:
+        raise ValueError(f"layered_placement must be one of {sorted(LAYERED_PLACEMENTS)}, got {placement!r}")
+    return LAYERED_PLACEMENTS[placement]
+
+
+def layered_info(handle, precision: int, placement: str = "auto") -> tuple[int, int, int, int]:
+    """Decoder.layered_info for a raw qd_graph handle (a host-only graph included)."""
+    out = np.zeros(4, np.int64)
+    _abi.check(_abi.load().qd_layered_info(handle, int(precision), layered_placement_code(placement), _abi.ptr(out)),
+               "qd_layered_info")
+    return tuple(int(v) for v in out)
+
+
+def layered_kernel_names() -> list[str]:
+    lib = _abi.load()
+    n = int(lib.qd_layered_kernel_names(None, 0))
+    if n < 0:
+        _abi.check(n, "qd_layered_kernel_names")
+    buf = C.create_string_buffer(n + 1)
+    lib.qd_layered_kernel_names(buf, n + 1)
+    return buf.value.decode().splitlines()
 
 
 def relay_info(handle, precision: int, placement: str = "auto") -> tuple[int, int, int, int]:

@@ -68,7 +68,7 @@ import scipy.sparse as sp
 
 from . import _abi
 from .codes import read_quantum_code
-from .decoder import Decoder
+from .decoder import Decoder, parse_schedule
 from .osd import OsdSolver
 from .spacetime import SpacetimeCode, SpacetimeCodeSingleShot
 from .storage_sim import build_storage_simulation
@@ -193,7 +193,7 @@ class DemPipeline:
         self.dec = Decoder(self.dem.fault_check_matrix, self.dem.fault_priors, method=o.get("bp_method", "ps"),
                            precision=precision, max_iter=int(o.get("max_iter", 0) or 0),
                            ms_scaling=float(o.get("ms_scaling_factor", 0.0)), logicals=fmap if self.k else None,
-                           device=self.device)
+                           device=self.device, schedule=o.get("bp_schedule", "flooding"))
         self.relay = relay is not None
         if self.relay:
             kw, self.relay_placement = relay_options(o, relay)
@@ -215,8 +215,8 @@ class DemPipeline:
         dev = torch.device("cuda", self.device)
         if self.osd:
             return self._run_osd(B, seed, stream_id, shot0, want_detail)
-        if self.relay:
-            packed = False  # the relay stage reads byte rows
+        if self.relay or self.dec.schedule == "layered":
+            packed = False  # the relay stage and the layered kernel read byte rows
         with torch.cuda.device(dev):
             det, faults, obs = sample_dem_device(self.dec, B, seed, stream_id, shot0, packed=packed,
                                                  want_obs=want_detail)
@@ -371,6 +371,13 @@ class BatchPipeline:
         o = bp_osd_options
         common = dict(method=o.get("bp_method", "ps"), precision=precision, max_iter=int(o.get("max_iter", 0) or 0),
                       ms_scaling=float(o.get("ms_scaling_factor", 0.0)), device=self.device)
+        # bp_schedule "layered": every BP stage of the mode (the windowed decoder's included) runs the
+        # check-serial schedule; OSD and relay follow it unchanged
+        self.bp_schedule = parse_schedule(o.get("bp_schedule", "flooding"))
+        if self.bp_schedule == "layered":
+            if mode in ("bpssf", "bpssf_hybrid"):
+                raise ValueError("bp_schedule='layered' does not run SSF: bpssf and bpssf_hybrid need the flooding schedule")
+            common["schedule"] = "layered"
         osd_method = o.get("osd_method", "osd_cs")
         osd_order = int(o.get("osd_order", 0))
         self.osd_method, self.osd_order = osd_method, osd_order
@@ -1264,6 +1271,9 @@ def p_sweep_main(noise_model_args, noise_model, meas_prior, data_prior):
     parser.add_argument("--window", type=int, default=None,
                         help="sliding-window decoding of bp / bposd: rounds per window (default: off, one graph over "
                              "all rounds)")
+    parser.add_argument("--bp_schedule", choices=["flooding", "layered"], default="flooding",
+                        help="BP schedule: flooding (every check, then every variable) or layered (check-serial "
+                             "min-sum; not with bpssf / bpssf_hybrid)")
     parser.add_argument("--commit", type=int, default=None,
                         help="rounds committed per window (default: max(1, window // 2))")
     parser.add_argument("--approximate_disjoint_errors", action="store_true",
@@ -1274,6 +1284,8 @@ def p_sweep_main(noise_model_args, noise_model, meas_prior, data_prior):
     bp_osd_options = unpack_bposd_args(args, code)
     if args.decoder_mode in ("bprelay", "bprelay_detector"):
         bp_osd_options.update(unpack_relay_args(args))
+    if args.bp_schedule == "layered":  # a flooding point keeps its checkpoint fingerprint and its CSV columns
+        bp_osd_options["bp_schedule"] = "layered"
     sweep =np.linspace(*args.p_sweep) if args.linspace else np.geomspace(*args.p_sweep)
     result = p_sweep(samples=args.samples, code=code, rounds=args.rounds, noise_model=noise_model,
                      noise_model_args=noise_model_args, meas_prior=meas_prior, data_prior=data_prior,

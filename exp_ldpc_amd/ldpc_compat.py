@@ -17,7 +17,10 @@ int ndarray of length n; afterwards ``.converge``, ``.iter``,
 ``.log_prob_ratios`` and ``.bp_decoding`` (and ``.osd0_decoding`` /
 ``.osdw_decoding``) are set as in ldpc.  ``decode_batch`` is the throughput
 path.  Extra: ``precision`` ('f64' = ldpc's double arithmetic, the default here;
-'f32'), ``device``.
+'f32'), ``device``, and ``schedule``: "flooding" (the default; ldpc v2 calls it
+"parallel", accepted as an alias) or "layered" (check-serial min-sum, DESIGN
+3.6f; with ``layered_clip`` and ``layered_placement`` as Decoder takes them).
+ldpc v2's "serial" is variable-serial, another algorithm, and is refused.
 
 ``relay_decoder`` has no ldpc counterpart: relay-BP (Decoder.set_relay /
 Decoder.relay) behind the same object interface.
@@ -27,7 +30,7 @@ from __future__ import annotations
 import numpy as np
 import scipy.sparse as sp
 
-from .decoder import Decoder, as_csr01, parse_bp_method
+from .decoder import Decoder, as_csr01, parse_bp_method, parse_schedule
 from . import _abi
 
 __all__ = ["bp_decoder", "bposd_decoder", "relay_decoder"]
@@ -65,11 +68,13 @@ class bp_decoder:
         self.bp_method = "product_sum" if self._method == _abi.QD_PRODUCT_SUM else "minimum_sum_log"
         self.ms_scaling_factor = float(kwargs.get("ms_scaling_factor", 1.0))
         self.input_vector_type = kwargs.get("input_vector_type", -1)
+        self.schedule = parse_schedule(kwargs.get("schedule", "flooding"))
         self.channel_probs = _resolve_probs(self.n, kwargs)
         self.error_rate = kwargs.get("error_rate", None)
         self._dec = Decoder(H, self.channel_probs, method=self._method, precision=kwargs.get("precision", "f64"),
                             max_iter=self.max_iter, ms_scaling=self.ms_scaling_factor,
-                            device=int(kwargs.get("device", 0)))
+                            device=int(kwargs.get("device", 0)), schedule=self.schedule,
+                            **{k: kwargs[k] for k in ("layered_clip", "layered_placement") if k in kwargs})
         self.converge = 0
         self.iter = 0
         self.bp_decoding = np.zeros(self.n, dtype=np.uint8)

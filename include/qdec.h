@@ -515,6 +515,80 @@ int qd_relay_set_slots(qd_graph* g, int64_t slots);
 int qd_relay_info(const qd_graph* g, int32_t precision, int32_t placement, int64_t out[4]);
 int64_t qd_relay_kernel_names(char* buf, int64_t cap);
 
+/* Layered (check-serial) min-sum BP: the rows of H are processed in ascending
+ * order and the posteriors are updated after each row, so information crosses
+ * the graph within an iteration; on the graphs here it leaves fewer shots open
+ * than the flooding schedule in about half the iterations.  The
+ * kernel runs one wave per shot with its lanes along the row, the access
+ * pattern wide rows (circuit detector error models) want.  Build-defined, fixed
+ * to the last rounding in DESIGN 3.6f with tests/layered_model.py as its model:
+ *   P_j = prior_j, R_e = 0; for t = 1 .. max_iter, for every row i in order,
+ *   over its edges e = (i, j): q_e = P_j - R_e; m1 <= m2 the two smallest |q_e|;
+ *   par = s_i ^ parity(q_e <= 0); y_e = min(|q_e| == m1 ? m2 a_t : m1 a_t, clip);
+ *   R_e = par ^ (q_e <= 0) ? -y_e : y_e; P_j = clamp(q_e + R_e, -clip, clip);
+ *   after the last row x_j = (P_j <= 0), and a shot with H x = s stops.
+ * a_t = ms_scaling, or 1 - 2^-t when ms_scaling = 0.  All arithmetic in T =
+ * float or double, no contraction.  The graph's min-sum priors are used.
+ *
+ * qd_layered_batch_device: B shots on device buffers, enqueued on `stream`.
+ * Inputs as qd_decode_batch_device's byte rows (syn_flags: QD_SYN_ADD_BASE /
+ * _READOUT).  Outputs (each nullable), with the meaning they have after
+ * qd_decode_batch_device, so the OSD and relay stages follow unchanged:
+ *   x_out    uint8 [B][n]      the hard decision after the last iteration run
+ *   corr_out uint8 [B][n_data] base ^ fold(x_out)
+ *   llr_out  [B][n] float / double: P as it stands
+ *   iters    int32 [B]         iterations run
+ *   status   uint8 [B]         3 (QD_ST_BP_CONVERGED | QD_ST_SATISFIED) when
+ *                              H x = s, else 0
+ *   fail     uint8 [B]         any(Lz (readout ^ corr_out)) (logicals + readout)
+ * placement: where a workgroup keeps P[n] and R[E] --
+ *   QD_LAYERED_LDS   dynamic LDS (-111 above 160 KiB)
+ *   QD_LAYERED_HBM   a slot of a scratch the handle owns, (E + n) sizeof(T)
+ *                    rounded to 256 B; the syndrome and the hard decision stay
+ *                    in LDS (-111 when they alone exceed 160 KiB)
+ *   QD_LAYERED_AUTO  LDS while eight workgroups fit a compute unit's 160 KiB,
+ *                    else HBM
+ * Both give the same bits.  The scratch follows the relay scratch's policy:
+ * grown on demand within a quarter of the free device memory (-113 when that
+ * holds no slot), halved on a refusal down to one slot (-112).  Launches on one
+ * handle from different streams are chained through an event.  Errors, in this
+ * order: -1 null handle, -4 precision, -8 B < 0, -68 placement, -49 a parameter
+ * out of range (null, max_iter < 1, ms_scaling not finite or < 0, clip not
+ * finite or <= 0; qd_layered_set_slots: slots outside 0 .. 2^20), -69 inputs
+ * the kernel does not take (QD_INPUT_PACKED, unknown syn_flags, a failure check
+ * over more than 256 logicals), -5 priors never set, -51 priors holding a 0 or
+ * a 1, -7 no syndrome source, -111, -16 host-only graph.  B = 0 returns 0 and
+ * writes nothing.
+ * qd_layered_batch: the same on host buffers, synchronous.
+ * qd_layered_set_slots: workgroups of later launches in both placements (0 =
+ * the default: 16 per compute unit in LDS or what its LDS holds, 8 in HBM); a
+ * launch uses at most B.
+ * Results do not depend on it.
+ * qd_layered_info: out[4] = kind (QD_LAYERED_LDS or QD_LAYERED_HBM) the
+ * placement launches, its dynamic LDS bytes, bytes per slot (0 for LDS),
+ * workgroups of the last launch.  No HIP call; host-only graphs answer.
+ * qd_layered_kernel_names: as qd_kernel_table_names for the layered kernels'
+ * own table (which that list does not include). */
+#define QD_LAYERED_LDS 0
+#define QD_LAYERED_HBM 1
+#define QD_LAYERED_AUTO 2
+typedef struct qd_layered_params {
+    int32_t max_iter;
+    double ms_scaling;
+    double clip;
+} qd_layered_params;
+int qd_layered_batch_device(qd_graph* g, const qd_layered_params* prm, int32_t precision, int64_t B,
+                            const uint8_t* syn, int32_t syn_flags, const uint8_t* base, const uint8_t* readout,
+                            uint8_t* x_out, uint8_t* corr_out, void* llr_out, int32_t* iters, uint8_t* status,
+                            uint8_t* fail, int32_t placement, void* stream);
+int qd_layered_batch(qd_graph* g, const qd_layered_params* prm, int32_t precision, int64_t B, const uint8_t* syn,
+                     int32_t syn_flags, const uint8_t* base, const uint8_t* readout, uint8_t* x_out,
+                     uint8_t* corr_out, void* llr_out, int32_t* iters, uint8_t* status, uint8_t* fail,
+                     int32_t placement);
+int qd_layered_set_slots(qd_graph* g, int64_t slots);
+int qd_layered_info(const qd_graph* g, int32_t precision, int32_t placement, int64_t out[4]);
+int64_t qd_layered_kernel_names(char* buf, int64_t cap);
+
 /* ---- sliding-window decoding: the step between two windows ----------------
  * (csrc/qdec_window.hip; no reference counterpart: the reference
  * left it as a stub, spacetime_code.py:95-96).  A layered graph is decoded
